@@ -25,6 +25,17 @@ resident frame (N = 1).  At N = 1 the line carries "insitu" (the in-situ
 frame through a one-rank RCCL communicator) and "ooc": configs[3], the
 frame with a 4-slot HBM cache of domain images streamed from pinned host
 memory (spray_rt_ooc_*).  Rank 0 prints one JSON line.
+
+A plain run (no --full) does only what the headline needs: scene and rays,
+warm-up, the timed steps, the outputs of --dump-outputs, the result line.
+--full adds everything else described above: the canonical traversal counts
+and the roofline objects, the unfused form, the "insitu", "insitu_protocol",
+"image_parallel", "ao", "frame" and "ooc" lines and the CPU baseline (each
+with its own switch, as before).
+
+--dump-outputs DIR writes what the last timed step left in the caller's
+buffers (dump_outputs below) as DIR/<name>.npy.  The rays are the same from
+run to run, so two builds can be compared array for array.
 """
 from __future__ import annotations
 
@@ -179,6 +190,47 @@ def cpu_baseline(target_s=10.0):
             "sample": "%d x the full 1024x1024x8spp frame (8 tiles of 1024x128): %d "
                       "primary+shadow rays, oracle/oracle.c (C, OpenMP, %d threads), "
                       "%.1f s traversal+spawn" % (reps, n, threads, dt)}
+
+
+DUMP_RAYS = 1 << 19  # sampled source rays: 76 B each as float32 / float64, 40 MB
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirname, hits, valid, occ, n_shadow):
+    """What a caller of spray_rt_intersect_scene_shadow_pt receives, for a
+    fixed seeded sample of DUMP_RAYS source rays (ascending indices,
+    sample_index.npy): the hit records field by field (float32; the integer
+    fields domain, prim and colour as float64, which holds them exactly),
+    shadow_valid / shadow_occluded per source ray, and shadow_rays.npy = the
+    launch's shadow-ray count.  The fields the interface leaves undefined are
+    written as 0: a missed ray's record apart from domain = -1, and occluded
+    where no shadow ray was spawned."""
+    import torch
+    from spray_amd._native import HIT_DTYPE
+    n = valid.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_RAYS, n),
+                                                          replace=False))
+    sel = torch.from_numpy(idx).to(hits.device)
+    rec = hits.view(-1, 48)[sel].cpu().numpy().view(HIT_DTYPE).reshape(-1)
+    v = valid[sel].cpu().numpy() != 0
+    o = (occ[sel].cpu().numpy() != 0) & v
+    hit = rec["domain"] >= 0
+
+    def field(name, dtype):
+        a = rec[name]
+        return np.where(hit.reshape((-1,) + (1,) * (a.ndim - 1)), a, 0).astype(dtype)
+
+    arrays = {"sample_index": idx.astype(np.float64),
+              "hit_domain": rec["domain"].astype(np.float64),
+              "hit_prim": field("prim", np.float64), "hit_color": field("color", np.float64),
+              "hit_t": field("t", np.float32),
+              "hit_uv": np.stack([field("u", np.float32), field("v", np.float32)], axis=1),
+              "hit_ng": field("ng", np.float32), "hit_ns": field("ns", np.float32),
+              "shadow_valid": v.astype(np.float32), "shadow_occluded": o.astype(np.float32),
+              "shadow_rays": np.array([n_shadow], np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 PARTITIONS = {"close": 0, "rr": 1, "view": 2}  # insitu.PARTITION_*
@@ -604,6 +656,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: canonical counts and "
+                         "rooflines, the unfused form, the insitu / image / ao / frame / ooc "
+                         "lines and the CPU baseline (the switches below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline", type=int, default=1)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--insitu", type=int, default=1,
@@ -673,24 +731,27 @@ def main():
     torch.cuda.synchronize()
 
     # ---- canonical traversal counts (counting build, outside the timing)
-    ctr = torch.zeros(3, dtype=torch.int64, device=dev)
-    ctr2 = torch.zeros(3, dtype=torch.int64, device=dev)
-    rt.intersect_scene(prim, hits, counters=ctr)
-    rt.spawn_shadows_pt(prim, hits, n_prim, SHADE, shadow, src, cnt)
-    rt.occluded_scene_devcount(shadow, n_prim, cnt, occ, counters=ctr2)
-    torch.cuda.synchronize()
-    n_shadow = int(cnt.item())
-    gpu_counts = {"primary": {"nodes": int(ctr[0]), "tris": int(ctr[1]), "visits": int(ctr[2]),
-                              "rays": n_prim},
-                  "shadow": {"nodes": int(ctr2[0]), "tris": int(ctr2[1]), "visits": int(ctr2[2]),
-                             "rays": n_shadow}}
-    counts_src = "gpu counting build"
-    if os.path.exists(COUNTS):
-        ref = json.load(open(COUNTS))
-        if ref.get("primary") == gpu_counts["primary"] and ref.get("shadow") == gpu_counts["shadow"]:
-            counts_src = "oracle fixture tests/golden/workload_counts.json (== gpu counting build)"
-        else:
-            counts_src = "gpu counting build (MISMATCH vs oracle fixture)"
+    if args.full:
+        ctr = torch.zeros(3, dtype=torch.int64, device=dev)
+        ctr2 = torch.zeros(3, dtype=torch.int64, device=dev)
+        rt.intersect_scene(prim, hits, counters=ctr)
+        rt.spawn_shadows_pt(prim, hits, n_prim, SHADE, shadow, src, cnt)
+        rt.occluded_scene_devcount(shadow, n_prim, cnt, occ, counters=ctr2)
+        torch.cuda.synchronize()
+        n_shadow = int(cnt.item())
+        gpu_counts = {"primary": {"nodes": int(ctr[0]), "tris": int(ctr[1]),
+                                  "visits": int(ctr[2]), "rays": n_prim},
+                      "shadow": {"nodes": int(ctr2[0]), "tris": int(ctr2[1]),
+                                 "visits": int(ctr2[2]), "rays": n_shadow}}
+        counts_src = "gpu counting build"
+        if os.path.exists(COUNTS):
+            ref = json.load(open(COUNTS))
+            if (ref.get("primary") == gpu_counts["primary"]
+                    and ref.get("shadow") == gpu_counts["shadow"]):
+                counts_src = ("oracle fixture tests/golden/workload_counts.json "
+                              "(== gpu counting build)")
+            else:
+                counts_src = "gpu counting build (MISMATCH vs oracle fixture)"
 
     rt.set_coherence(rt.RAYS_COHERENT)  # camera rays and point-light shadow rays
 
@@ -729,11 +790,64 @@ def main():
         e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
-    assert int(nsh.item()) == n_shadow
+    if args.full:
+        assert int(nsh.item()) == n_shadow
+    n_shadow = int(nsh.item())  # the shadow rays the last timed step spawned
     fused_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))
     ms_step = elapsed / args.steps * 1e3
     rays_step = n_prim + n_shadow
     value = rays_step * world * args.steps / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hits, valid, occ, n_shadow)
+
+    out = {
+        "metric": METRIC, "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic (reference example mesh wavelet.ply x64, deterministic camera rays)",
+        "config": {"workload": "wavelets64 1024x1024x8spp PT primary+shadow, all 64 domains "
+                               "resident per GPU (configs[1])",
+                   "rays_per_step": rays_step, "primary_rays": n_prim, "shadow_rays": n_shadow,
+                   "parallelism": "one GPU, the whole frame"},
+        "kernels_ms": {"intersect_scene_shadow_pt": round(fused_ms, 4)},
+    }
+    if args.full:
+        full_lines(args, out, dist, world, rank, local, sc, rt, cam, prim, pixid, n_prim,
+                   n_shadow, fused_ms, gpu_counts, counts_src, step_unfused)
+    elif world > 1:
+        # the N > 1 headline is the domain-parallel in-situ frame
+        insitu_headline(args, out, run_insitu(args, dist, world, rank, local, cam), world)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    sc.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def insitu_headline(args, out, ins, world):
+    """configs[2] is the N > 1 headline: the frame split across the GPUs by
+    domain (strong scaling); the frame replicas stay as a secondary key."""
+    out["insitu"] = ins
+    out["replicas"] = {"value": out["value"], "ms_per_step": out["ms_per_step"],
+                       "scaling": "weak",
+                       "config": "configs[1] frame replicas x%d (every GPU traces the "
+                                 "whole frame; no data-path collective)" % world}
+    out["value"], out["ms_per_step"] = ins["value"], ins["ms_per_step"]
+    out["config"] = {"workload": ins["config"], "rays_per_step": ins["rays_per_step"],
+                     "primary_rays": ins["radiance_rays"], "shadow_rays": ins["shadow_rays"],
+                     "parallelism": "domain-parallel in-situ x%d (strong), %s partition%s"
+                                    % (world, args.partition,
+                                       " (NOT the reference's: its compiled GROUP_CLOSE is "
+                                       "timed under insitu_partitions.close)"
+                                       if args.partition != "close" else
+                                       " (the reference's compiled GROUP_CLOSE)")}
+
+
+def full_lines(args, out, dist, world, rank, local, sc, rt, cam, prim, pixid, n_prim, n_shadow,
+               fused_ms, gpu_counts, counts_src, step_unfused):
+    """--full: everything the result line carries beside the headline."""
+    import torch
+    import spray_amd
 
     # the two-launch form of the same step, for comparison (untimed by the
     # step clock above)
@@ -753,24 +867,13 @@ def main():
     # shadow valid / occluded bytes out (the shadow rays never leave the chip),
     # the scene image once
     fused_compulsory = n_prim * (32 + 48 + 1 + 1) + sbytes
-    out = {
-        "metric": METRIC, "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic (reference example mesh wavelet.ply x64, deterministic camera rays)",
-        "config": {"workload": "wavelets64 1024x1024x8spp PT primary+shadow, all 64 domains "
-                               "resident per GPU (configs[1])",
-                   "rays_per_step": rays_step, "primary_rays": n_prim, "shadow_rays": n_shadow,
-                   "parallelism": "one GPU, the whole frame"},
-        "roofline": roofline(KERNEL_FUSED, fused_ms * 1e-3, fused_compulsory, fused_bytes,
-                             "SURVEY 8(d) per-ray node/triangle bytes over the canonical counts "
-                             "(%s); a work index, not traffic (one node fetch per wave, scene "
-                             "in L2/MALL)" % counts_src),
-        "kernels_ms": {"intersect_scene_shadow_pt": round(fused_ms, 4),
-                       "unfused": {"intersect_scene_spawn_pt": round(ch_ms, 4),
-                                   "occluded_scene_masked": round(ah_ms, 4)}},
-        "canonical_counts": gpu_counts,
-    }
+    out["roofline"] = roofline(KERNEL_FUSED, fused_ms * 1e-3, fused_compulsory, fused_bytes,
+                               "SURVEY 8(d) per-ray node/triangle bytes over the canonical "
+                               "counts (%s); a work index, not traffic (one node fetch per wave, "
+                               "scene in L2/MALL)" % counts_src)
+    out["kernels_ms"]["unfused"] = {"intersect_scene_spawn_pt": round(ch_ms, 4),
+                                    "occluded_scene_masked": round(ah_ms, 4)}
+    out["canonical_counts"] = gpu_counts
     if args.insitu != 0 or world > 1:
         out["insitu"] = run_insitu(args, dist, world, rank, local, cam)
     if world == 1 and args.insitu != 0:
@@ -785,22 +888,7 @@ def main():
                                             partition=p).items()
                 if k in ("value", "ms_per_step", "rank0_phases_ms")}
             for p in PARTITIONS if p != args.partition}
-        # configs[2] is the N > 1 headline: the frame split across the GPUs by
-        # domain (strong scaling); the frame replicas stay as a secondary key
-        ins = out["insitu"]
-        out["replicas"] = {"value": out["value"], "ms_per_step": out["ms_per_step"],
-                           "scaling": "weak",
-                           "config": "configs[1] frame replicas x%d (every GPU traces the "
-                                     "whole frame; no data-path collective)" % world}
-        out["value"], out["ms_per_step"] = ins["value"], ins["ms_per_step"]
-        out["config"] = {"workload": ins["config"], "rays_per_step": ins["rays_per_step"],
-                         "primary_rays": ins["radiance_rays"], "shadow_rays": ins["shadow_rays"],
-                         "parallelism": "domain-parallel in-situ x%d (strong), %s partition%s"
-                                        % (world, args.partition,
-                                           " (NOT the reference's: its compiled GROUP_CLOSE is "
-                                           "timed under insitu_partitions.close)"
-                                           if args.partition != "close" else
-                                           " (the reference's compiled GROUP_CLOSE)")}
+        insitu_headline(args, out, out["insitu"], world)
     if args.image:
         out["image_parallel"] = run_image(args, dist, world, rank, local, cam)
     if args.ao:
@@ -815,11 +903,6 @@ def main():
         out["ooc"] = run_ooc(args, rt, prim, n_prim)
     if rank == 0 and world == 1 and args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    sc.close()
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

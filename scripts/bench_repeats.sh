@@ -4,7 +4,7 @@ set -u
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${TAG:-rep}; mkdir -p "$OUT"
 for k in $(seq 1 ${R:-3}); do
-  timeout -k 10 200 python -u bench.py --steps 100 --warmup 20 --insitu 0 --ao 0 --frame 0 \
+  timeout -k 10 200 python -u bench.py --full --steps 100 --warmup 20 --insitu 0 --ao 0 --frame 0 \
     --image 0 --ooc 0 --cpu-baseline 0 > "$OUT/b$k.json" 2>/dev/null || exit 1
   python3 - "$OUT/b$k.json" <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${TAG:-check}; mkdir -p "$OUT"
 timeout -k 10 600 python -u -m pytest -x -q --timeout 120 --timeout-method thread ${TESTS:-tests} -m gpu > "$OUT/test.log" 2>&1 || { tail -30 "$OUT/test.log"; exit 1; }
 tail -2 "$OUT/test.log"
-timeout -k 10 300 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python3 - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-sq}; mkdir -p "$OUT"
 timeout -s KILL 60 rocprofv3 -L > "$OUT/avail.txt" 2>&1
 grep -o "SQ_[A-Z_0-9]*" "$OUT/avail.txt" | sort -u > "$OUT/sq_names.txt"; wc -l "$OUT/sq_names.txt"
-BENCH="python3 bench.py --steps 3 --warmup 1 --cpu-baseline 0 --ao ${AO:-0} --ooc 0 --frame 0"
+BENCH="python3 bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --ao ${AO:-0} --ooc 0 --frame 0"
 i=0
 for G in "$@"; do
   i=$((i+1))

@@ -2,7 +2,7 @@
 set -u
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-trace}; mkdir -p "$OUT"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run -- python3 bench.py ${ARGS:---steps 5 --warmup 2 --cpu-baseline 0} > "$OUT/bench.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o run -- python3 bench.py --full ${ARGS:---steps 5 --warmup 2 --cpu-baseline 0} > "$OUT/bench.log" 2>&1
 rc=$?; echo "trace rc=$rc"; tail -2 "$OUT/bench.log"
 python3 - "$OUT" <<'PY'
 import csv, sys, glob

@@ -9,7 +9,7 @@ if [ "${TESTS:-0}" = 1 ]; then
 fi
 for rep in 1 2; do
   for p in ${PERS:-0 4}; do
-    SPRAY_OOC_PER=$p timeout -k 10 300 python bench.py --steps 10 --warmup 3 --ao 0 --frame 0 --insitu 0 --cpu-baseline 0 > "$OUT/bench_${p}_$rep.log" 2>&1 || { tail -5 "$OUT/bench_${p}_$rep.log"; exit 1; }
+    SPRAY_OOC_PER=$p timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --ao 0 --frame 0 --insitu 0 --cpu-baseline 0 > "$OUT/bench_${p}_$rep.log" 2>&1 || { tail -5 "$OUT/bench_${p}_$rep.log"; exit 1; }
     python -c "
 import json; l=[x for x in open('$OUT/bench_${p}_$rep.log') if x.startswith('{')][-1]; d=json.loads(l); o=d['ooc']; print('per=$p', o['ms_per_step'], o['loads_per_step'])"
   done

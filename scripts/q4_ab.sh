@@ -12,7 +12,7 @@ for rep in 1 2; do
   for L in shipped ${LIBS:-}; do
     if [ $L = shipped ]; then unset SPRAY_RT_LIB; else export SPRAY_RT_LIB=$PWD/$L; fi
     n=$(basename $L .so)
-    timeout -k 10 200 python bench.py --steps 10 --warmup 3 --cpu-baseline 0 --ooc 0 --frame 0 --insitu 0 > "$OUT/bench_${n}_$rep.log" 2>&1 || { tail -5 "$OUT/bench_${n}_$rep.log"; exit 1; }
+    timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --cpu-baseline 0 --ooc 0 --frame 0 --insitu 0 > "$OUT/bench_${n}_$rep.log" 2>&1 || { tail -5 "$OUT/bench_${n}_$rep.log"; exit 1; }
     python -c "
 import json; l=[x for x in open('$OUT/bench_${n}_$rep.log') if x.startswith('{')][-1]; d=json.loads(l); a=d['ao']; print('$n', d['ms_per_step'], a['ms_per_step'], a['roofline']['avg_launch_ms'])"
   done

@@ -116,9 +116,9 @@ def main(src, tag):
     build_id = json.load(open(binfo)).get("build_id") if os.path.exists(binfo) else None
     out = {"round": tag, "source": src, "build_id": build_id, "kernels": {}}
     lines = ["# rocprofv3 summary, %s (library build %s)" % (tag, build_id), "",
-             "Kernel trace: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 "
+             "Kernel trace: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 "
              "--warmup 5 --cpu-baseline 0`.  PMC: one `rocprofv3 --pmc <set>` pass per counter "
-             "set of `bench.py --steps 2 --warmup 1 --cpu-baseline 0 --ooc 0 --frame 0 "
+             "set of `bench.py --full --steps 2 --warmup 1 --cpu-baseline 0 --ooc 0 --frame 0 "
              "--insitu 0` (scripts/gpu_profile.sh); raw counters in `%s_pmc.csv`; derivations "
              "in scripts/summarize_profiles.py." % tag, "",
              "| kernel | calls | avg us | traffic B | HBM frac | L2 hit | L2 req frac | "
