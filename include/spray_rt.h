@@ -166,6 +166,77 @@ int spray_rt_qnodes4_host(const float* verts_xyz, size_t nverts, const uint32_t*
                           size_t nfaces, size_t* nnodes, int* stack_bound, float grid_out[6],
                           void* qnodes_out);
 
+/* ---- moving geometry: refit of resident slots ---- */
+/* New vertex positions for resident slots whose topology (faces) is unchanged.
+ * verts[i]: [nverts of slots[i]][3] floats, world space; vnormals[i]: the new
+ * unnormalised vertex normals, required iff the slot was uploaded with normals
+ * (vnormals itself may be NULL when no slot has any).  Pointers may be device or
+ * host memory (host: staged, and the call returns with the work completed), as
+ * for ray buffers.  d_bounds (optional, device float[n][6]) receives each
+ * slot's new exact, unpadded lo.xyz hi.xyz: the caller re-issues
+ * spray_rt_domain_bounds when the geometry left its domain box (then
+ * spray_rt_map_domain and spray_rt_set_owners again: that call resets both).
+ * One host read of n status words per call, however many slots; ordered after
+ * queued work on the context's stream and before the next query.
+ *
+ * What is kept: faces, the leaf order, leaf ranges, child refs, the 4-wide
+ * collapse and its child refs, the tree depth and the walks' stack bound.
+ * What is recomputed on the device with the builder's own arithmetic: every
+ * BVH2 child box (exact min/max of its subtree's new vertices, then the
+ * builder's padding), every triangle record, the quantization grid, every
+ * 4-wide child box, the normals.  Closest hits do not depend on the tree
+ * (the minimum of (t, primID)), so queries after a refit return the bits a
+ * fresh spray_rt_domain_upload of the new vertices returns; a refit with the
+ * vertices a slot was built from reproduces its image byte for byte (up to
+ * the sign of a zero box bound of a mesh that holds both +0 and -0).  The
+ * tree is only as good as the old topology allows on the new positions:
+ * watch spray_rt_slot_sah and rebuild with spray_rt_domain_upload when it
+ * has grown too far.
+ *
+ * A failed call leaves every slot of the call exactly as it was (all
+ * validation happens before any slot memory is written): SPRAY_RT_ERR_ARG
+ * for an unloaded slot, a slot listed twice, a NULL vertex pointer, a
+ * missing normal array where the slot has normals, or a non-finite
+ * coordinate (or edge) of a referenced vertex; SPRAY_RT_ERR_LIMIT when a box
+ * cannot be quantized.  spray_rt_last_error names the slot.
+ *
+ * Deliberately left out: the images of the out-of-core cache
+ * (spray_rt_ooc_set_domain; they carry no refit metadata), the scene layer's
+ * domain cache (include/spray_scene.h, spray_scene.hpp: a cache miss uploads
+ * the image built from the file again), and changing topology (a device
+ * build).  Not for use while lanes run (they read the slot tables). */
+int spray_rt_domains_refit(spray_rt_ctx_t ctx, int n, const int* slots,
+                           const float* const* verts, const float* const* vnormals,
+                           float* d_bounds);
+/* Host-only restatement (no GPU): the image a refit produces from the canonical
+ * build of (verts0, faces) and new_verts.  Same output conventions as
+ * spray_rt_bvh_build_host / spray_rt_qnodes4_host (any output may be NULL;
+ * sizes as those calls report them for (verts0, faces)).  SPRAY_RT_ERR_ARG /
+ * SPRAY_RT_ERR_LIMIT as spray_rt_domains_refit. */
+int spray_rt_bvh_refit_host(const float* verts0, const float* new_verts, size_t nverts,
+                            const uint32_t* faces, size_t nfaces, void* nodes_out,
+                            float* tris_out, float grid_out[6], void* qnodes4_out);
+/* Read back one array of a resident slot (tests, debugging): *nbytes = its
+ * size; with out, copied there (cap_bytes >= the size) after the queued work
+ * on the context's stream.  Slots without the quantized copy report 0 bytes
+ * for QNODES4 and QGRID, slots without normals 0 for NORMALS. */
+#define SPRAY_RT_SLOT_NODES 0   /* BvhNode[]  */
+#define SPRAY_RT_SLOT_TRIS 1    /* float[ntris][12] */
+#define SPRAY_RT_SLOT_PRIMS 2   /* uint32[ntris] leaf order -> face */
+#define SPRAY_RT_SLOT_QNODES4 3 /* QNode4[], index order */
+#define SPRAY_RT_SLOT_QGRID 4   /* float[6] base, scale */
+#define SPRAY_RT_SLOT_NORMALS 5 /* float[nverts][3] */
+int spray_rt_slot_export(spray_rt_ctx_t ctx, int slot, int what, void* out, size_t cap_bytes,
+                         size_t* nbytes);
+/* SAH cost of the slot's current BVH2, so a caller can tell when refits have
+ * degraded the tree enough to rebuild with spray_rt_domain_upload.
+ * Sum over nodes, over each non-empty child c, of
+ * half_area(c) * (c is a leaf ? its triangle count : 1), divided by half_area of
+ * the union of node 0's child boxes.  half_area on the stored padded boxes in
+ * float as (dx*dy + dy*dz) + dz*dx; the sum in double, in a fixed order
+ * (deterministic).  Synchronises the context's stream. */
+int spray_rt_slot_sah(spray_rt_ctx_t ctx, int slot, double* out);
+
 /* ---- Embree-1M-style streams (drop-in) ---- */
 int spray_rt_intersect1M(spray_rt_ctx_t ctx, int slot, void* rays, size_t M,
                          size_t stride);

@@ -77,6 +77,10 @@ SIGNATURES = {
     "spray_rt_bvh_build_host": (I, [P, SZ, P, SZ, P, P, P, P, P]),
     "spray_rt_qnodes_host": (I, [P, SZ, P, SZ, P, P, P]),
     "spray_rt_qnodes4_host": (I, [P, SZ, P, SZ, P, P, P, P]),
+    "spray_rt_domains_refit": (I, [P, I, P, P, P, P]),
+    "spray_rt_bvh_refit_host": (I, [P, P, SZ, P, SZ, P, P, P, P]),
+    "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
+    "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),
     "spray_rt_occluded1M": (I, [P, I, P, SZ, SZ]),
     "spray_rt_intersect_segments": (I, [P, P, P, I, P, SZ]),
@@ -178,7 +182,8 @@ _lib = None
 
 
 class SprayRtError(RuntimeError):
-    pass
+    """code: the engine's status (SPRAY_RT_ERR_*) when the failure carries one."""
+    code = None
 
 
 def lib():

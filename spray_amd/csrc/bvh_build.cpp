@@ -398,6 +398,7 @@ struct Collapse {
   std::vector<QNode4>* out;
   std::vector<int> height;  // BVH2 inner levels below (leaf 0)
   int budget;
+  std::vector<int32_t>* src = nullptr;  // per QNode4 child: BVH2 node << 1 | side, -1 empty
   int bound = 0;
   bool ok = true;
 
@@ -405,6 +406,7 @@ struct Collapse {
     const float* lo;
     const float* hi;
     int32_t ref;
+    int32_t src;  // the BVH2 (node << 1 | side) whose box this is
   };
   int h_of(int32_t ref) const { return ref >= 0 ? height[size_t(ref)] : 0; }
   static float area(const Cand& c) {
@@ -413,8 +415,8 @@ struct Collapse {
   }
   void children(int32_t node, std::vector<Cand>* cs) const {
     const BvhNode& n = n2[size_t(node)];
-    if (n.left != kNoChild && !empty_box(n.l_lo)) cs->push_back({n.l_lo, n.l_hi, n.left});
-    if (n.right != kNoChild && !empty_box(n.r_lo)) cs->push_back({n.r_lo, n.r_hi, n.right});
+    if (n.left != kNoChild && !empty_box(n.l_lo)) cs->push_back({n.l_lo, n.l_hi, n.left, node * 2});
+    if (n.right != kNoChild && !empty_box(n.r_lo)) cs->push_back({n.r_lo, n.r_hi, n.right, node * 2 + 1});
   }
   int32_t emit(int32_t node, int pend) {
     std::vector<Cand> cs;
@@ -449,6 +451,10 @@ struct Collapse {
     const int32_t id = int32_t(out->size());
     out->push_back(QNode4{});
     const int k = int(cs.size());
+    if (src) {
+      src->resize(out->size() * 4, -1);
+      for (int c = 0; c < k; ++c) (*src)[size_t(id) * 4 + size_t(c)] = cs[size_t(c)].src;
+    }
     const int p2 = pend + (k > 0 ? k - 1 : 0);
     bound = std::max(bound, p2);
     QNode4 q{};
@@ -485,8 +491,10 @@ bool quantize_nodes(const std::vector<BvhNode>& nodes, QGrid* grid,
 }
 
 bool quantize_nodes4(const std::vector<BvhNode>& nodes, QGrid* grid,
-                     std::vector<QNode4>* out, int* stack_bound) {
+                     std::vector<QNode4>* out, int* stack_bound,
+                     std::vector<int32_t>* child_src) {
   out->clear();
+  if (child_src) child_src->clear();
   if (stack_bound) *stack_bound = 0;
   if (!make_qgrid(nodes, grid)) return false;
   if (nodes.empty()) return true;
@@ -498,9 +506,30 @@ bool quantize_nodes4(const std::vector<BvhNode>& nodes, QGrid* grid,
     if (stack_bound) *stack_bound = c.height[0];
     return false;
   }
+  c.src = child_src;
   c.emit(0, 0);
   if (stack_bound) *stack_bound = c.bound;
   return c.ok && c.bound <= kQ4Stack;
+}
+
+void refit_order(const std::vector<BvhNode>& nodes, std::vector<uint32_t>* order,
+                 uint32_t level[kRefitLevels], int* height) {
+  order->clear();
+  for (int h = 0; h < kRefitLevels; ++h) level[h] = 0;
+  *height = 0;
+  const size_t n = nodes.size();
+  if (n == 0) return;
+  std::vector<int> hgt(n, 0);
+  auto h_of = [&](int32_t ref) { return ref >= 0 ? hgt[size_t(ref)] : 0; };
+  // depth-first layout: children follow their parent
+  for (size_t i = n; i-- > 0;) hgt[i] = 1 + std::max(h_of(nodes[i].left), h_of(nodes[i].right));
+  *height = hgt[0];
+  // counting sort by height, stable in the node index; level[h] = first entry of height h
+  for (size_t i = 0; i < n; ++i) ++level[hgt[i] + 1];
+  for (int h = 1; h < kRefitLevels; ++h) level[h] += level[h - 1];
+  order->resize(n);
+  std::vector<uint32_t> next(level, level + kRefitLevels);
+  for (size_t i = 0; i < n; ++i) (*order)[next[hgt[i]]++] = uint32_t(i);
 }
 
 }  // namespace spray_rt

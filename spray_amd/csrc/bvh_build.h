@@ -40,8 +40,19 @@ bool quantize_nodes(const std::vector<BvhNode>& nodes, QGrid* grid,
 // boxes quantized on the same grid as quantize_nodes.  stack_bound = the
 // most entries the walk can hold pending (every entered child but the
 // nearest pushed), <= kQ4Stack.  Node 0 is the root, children after parents.
+// child_src (optional): entry 4 i + c = the BVH2 (node << 1 | side) whose box
+// child c of QNode4 i quantizes, -1 for an empty child -- what a refit needs
+// to requantize without running the collapse again.
 bool quantize_nodes4(const std::vector<BvhNode>& nodes, QGrid* grid,
-                     std::vector<QNode4>* out, int* stack_bound);
+                     std::vector<QNode4>* out, int* stack_bound,
+                     std::vector<int32_t>* child_src = nullptr);
+
+// Order of a bottom-up refit: the nodes sorted by height (1 + the larger
+// child height, leaves 0; ties by index), and level[h] = the first entry of
+// height h (level[0] = level[1] = 0, level[h] = nodes.size() for h > height).
+// Every inner child of a node of height h sits at a lower height.
+void refit_order(const std::vector<BvhNode>& nodes, std::vector<uint32_t>* order,
+                 uint32_t level[kRefitLevels], int* height);
 
 // Top-level tree over domain boxes [n][6] (lo, hi): same builder, one domain
 // per leaf (ref ~(id << 2)), EXACT union boxes (no padding) so that the

@@ -82,8 +82,9 @@ const char* build_slot_image(const float* verts, size_t nverts, const uint32_t* 
       if (!std::isfinite(img.tris[12 * i + k])) return "non-finite vertex coordinate";
   QGrid grid{};
   std::vector<QNode4> qn;
+  std::vector<int32_t> qsrc;  // refit metadata: the BVH2 source of every QNode4 child
   int qstack = 0;  // <= kQ4Stack, which the any-hit launches provide
-  if (quantized && !img.nodes.empty() && !quantize_nodes4(img.nodes, &grid, &qn, &qstack))
+  if (quantized && !img.nodes.empty() && !quantize_nodes4(img.nodes, &grid, &qn, &qstack, &qsrc))
     return qstack > kQ4Stack ? "4-wide node collapse exceeds the any-hit walk's stack (kQ4Stack)"
                              : "vertex coordinates beyond the range of the quantized node grid";
   // QGrid at nodes - 32, QNode4 i at nodes - 64 - 64 (i + 1) (rt_common.h)
@@ -94,8 +95,17 @@ const char* build_slot_image(const float* verts, size_t nverts, const uint32_t* 
   const size_t b_faces = align256(3 * nfaces * sizeof(uint32_t));
   const size_t b_colors = colors ? align256(nverts * sizeof(uint32_t)) : 0;
   const size_t b_normals = normals ? align256(3 * nverts * sizeof(float)) : 0;
-  out->bytes.assign(
-      std::max<size_t>(256, b_q + b_nodes + b_tris + b_prims + b_faces + b_colors + b_normals), 0);
+  std::vector<uint32_t> order;
+  out->refit = RefitInfo{};
+  if (quantized) {
+    refit_order(img.nodes, &order, out->refit.level, &out->refit.height);
+    out->refit.nq = uint32_t(qn.size());
+  }
+  const size_t b_refit =
+      quantized ? align256((order.size() + kRefitLevels + qsrc.size()) * sizeof(uint32_t)) : 0;
+  out->bytes.assign(std::max<size_t>(256, b_q + b_nodes + b_tris + b_prims + b_faces + b_colors +
+                                              b_normals + b_refit),
+                    0);
   out->nbytes = out->bytes.size();
   char* host = out->bytes.data();
   size_t off = 0;
@@ -117,6 +127,13 @@ const char* build_slot_image(const float* verts, size_t nverts, const uint32_t* 
   out->o_faces = put(faces, 3 * nfaces * sizeof(uint32_t), b_faces);
   out->o_colors = colors ? put(colors, nverts * sizeof(uint32_t), b_colors) : SIZE_MAX;
   out->o_normals = normals ? put(normals, 3 * nverts * sizeof(float), b_normals) : SIZE_MAX;
+  if (quantized) {
+    out->refit.offset = off;
+    if (!order.empty()) std::memcpy(host + off, order.data(), order.size() * 4);
+    std::memcpy(host + out->refit.o_level(order.size()), out->refit.level, kRefitLevels * 4);
+    if (!qsrc.empty())
+      std::memcpy(host + out->refit.o_qsrc(order.size()), qsrc.data(), qsrc.size() * 4);
+  }
   out->nnodes = uint32_t(img.nodes.size());
   out->ntris = uint32_t(img.prims.size());
   out->nverts = uint32_t(nverts);
@@ -164,6 +181,7 @@ int upload_slot_image(spray_rt_ctx* c, int slot, const SlotImage& img, const voi
   }
   sh.desc = img.desc_at(d);
   sh.depth = img.depth;
+  sh.refit = img.refit;
   c->slots_dirty = true;
   return SPRAY_RT_OK;
 }
@@ -365,9 +383,11 @@ int spray_rt_destroy(spray_rt_ctx_t c) {
   }
   void* bufs[] = {c->d_slots, c->d_boxes, c->d_dom2slot, c->d_domtrav, c->d_owner, c->d_tlas, c->d_seg_slot,
                   c->d_seg_off, c->d_stage, c->d_stage2, c->d_stage3,
-                  c->d_block_counts, c->d_heads, c->d_sel, c->d_bsdf, c->d_frame, c->d_fstats, c->d_ftab};
+                  c->d_block_counts, c->d_heads, c->d_sel, c->d_bsdf, c->d_frame, c->d_fstats, c->d_ftab,
+                  c->d_refit, c->d_sah};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  if (c->h_refit) (void)hipHostFree(c->h_refit);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
   delete c;
@@ -472,6 +492,7 @@ int spray_rt_domain_release(spray_rt_ctx_t c, int slot) {
   sh.dmem = nullptr;
   sh.bytes = 0;
   sh.desc = SlotDesc{};
+  sh.refit = RefitInfo{};
   c->slots_dirty = true;
   return SPRAY_RT_OK;
 }

@@ -8,6 +8,8 @@
 //   faces  : uint32[3 * nfaces]     epilogue gather (PLY order)
 //   colors : uint32[nverts]         0xRRGGBB per vertex
 //   normals: float[3 * nverts]      unnormalised vertex normals
+//   refit  : uint32 order | level | qsrc  scene slots: what a refit in place
+//                                         needs (rt_ctx.h RefitInfo)
 // A device-side SlotDesc table points at these; the scene path adds a
 // domain -> slot map and the domain AABBs.
 #pragma once
@@ -77,6 +79,10 @@ constexpr int kQ4Stack = 40;
 // caps at kMaxDepth (+1 for the root level): a tree the builder accepts always
 // fits the 4-wide walk's stack, so quantize_nodes4 fails only on the grid
 static_assert(kMaxDepth + 1 <= kQ4Stack, "4-wide walk stack below the BVH2 height bound");
+// entries of a refit's level table (bvh_build.h refit_order): heights 0 ..
+// kMaxDepth + 1 and one end entry
+constexpr int kRefitLevels = 32;
+static_assert(kMaxDepth + 3 <= kRefitLevels, "level table below the BVH2 height bound");
 struct alignas(16) QGrid {
   float base[3];
   float pad0;

@@ -16,11 +16,27 @@
 namespace spray_rt {
 namespace detail {
 
+// Refit metadata of a slot image (spray_rt_domains_refit), appended behind
+// the image's arrays at byte `offset`, 256-B aligned:
+//   order : uint32[nnodes]        nodes by height (bvh_build.h refit_order)
+//   level : uint32[kRefitLevels]  first entry of each height
+//   qsrc  : int32[4 * nq]         BVH2 (node << 1 | side) of each QNode4 child
+// Images built without the quantized copy (OOC) carry none.
+struct RefitInfo {
+  size_t offset = SIZE_MAX;  // SIZE_MAX: absent
+  uint32_t nq = 0;           // QNode4 count
+  int height = 0;            // BVH2 height (levels of the bottom-up fit)
+  uint32_t level[kRefitLevels] = {};
+  size_t o_level(size_t nnodes) const { return offset + nnodes * 4; }
+  size_t o_qsrc(size_t nnodes) const { return o_level(nnodes) + size_t(kRefitLevels) * 4; }
+};
+
 struct SlotHost {
-  void* dmem = nullptr;  // one allocation: nodes|tris|prims|faces|colors|normals
+  void* dmem = nullptr;  // one allocation: nodes|tris|prims|faces|colors|normals|refit metadata
   size_t bytes = 0;
   SlotDesc desc{};
   int depth = 0;
+  RefitInfo refit;
   hipEvent_t ready = nullptr;  // async upload completion
   void* pinned = nullptr;      // staging for async uploads
   size_t pinned_bytes = 0;
@@ -71,6 +87,11 @@ struct spray_rt_ctx {
   size_t stage2_cap = 0;
   void* d_stage3 = nullptr;
   size_t stage3_cap = 0;
+  void* d_refit = nullptr;  // refit job table, status words and scratch image
+  size_t refit_cap = 0;
+  void* h_refit = nullptr;  // pinned mirror of the job table and the status words
+  size_t h_refit_cap = 0;
+  double* d_sah = nullptr;  // spray_rt_slot_sah's result
   uint32_t* d_block_counts = nullptr;
   // work-queue heads of the persistent launches: [0, kHeadsBytes) zeroed by
   // each launch, [kHeadsBytes, 2 kHeadsBytes) zeroed by a frame's launch_clear
@@ -114,10 +135,10 @@ namespace detail {
 
 // Device image of one domain, packed on the host: [quantized nodes + grid]
 // | BVH2 nodes | triangle records | leaf->face map | faces | colors |
-// normals, 256-B aligned (the HBM slot layout of rt_common.h).  The
-// quantized copy (QNode, in front of the nodes) is built for scene slots
-// only (quantized = true): the OOC drains do not read it, so its images
-// stream without it.
+// normals | refit metadata, 256-B aligned (the HBM slot layout of
+// rt_common.h).  The quantized copy (QNode, in front of the nodes) and the
+// refit metadata are built for scene slots only (quantized = true): the OOC
+// drains do not read them, so its images stream without them.
 struct SlotImage {
   std::vector<char> bytes;  // may be released once a pinned copy exists
   size_t nbytes = 0;        // the image's size (== bytes.size() while held)
@@ -125,6 +146,7 @@ struct SlotImage {
   size_t o_colors = SIZE_MAX, o_normals = SIZE_MAX;  // SIZE_MAX: absent
   uint32_t nnodes = 0, ntris = 0, nverts = 0;
   int depth = 0;
+  RefitInfo refit;
   // descriptor of the image once copied to device address base
   SlotDesc desc_at(const void* base) const;
 };

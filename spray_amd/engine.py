@@ -16,6 +16,7 @@ from ._native import (HIT_DTYPE, INVALID_ID, RAY_DTYPE, RTC_ISECT_DTYPE, BsdfRec
                       SprayRtError, lib)
 
 __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_rays",
+           "bvh_refit_host",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
            "HIT_DTYPE", "RTC_ISECT_DTYPE", "INVALID_ID", "SprayRtError"]
@@ -70,6 +71,39 @@ def make_rays(org, dir, tnear=0.001, tfar=np.inf):
     r["tnear"] = tnear
     r["tfar"] = tfar
     return r
+
+
+def bvh_refit_host(verts0, new_verts, faces):
+    """spray_rt_bvh_refit_host (no GPU): the image a refit of the canonical
+    build of (verts0, faces) to new_verts produces -> dict of nodes (uint8
+    [nnodes, 64]), tris (float32 [ntris, 12]), grid (float32 [6]), qnodes4
+    (uint8 [nq, 64])."""
+    v0 = np.ascontiguousarray(verts0, np.float32).reshape(-1, 3)
+    v1 = np.ascontiguousarray(new_verts, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    if v0.shape != v1.shape:
+        raise ValueError("new_verts must have the shape of verts0")
+    L = lib()
+    nn, nq = C.c_size_t(), C.c_size_t()
+    if L.spray_rt_bvh_build_host(v0.ctypes.data, len(v0), f.ctypes.data, len(f), C.byref(nn),
+                                 None, None, None, None) != 0:
+        raise SprayRtError("bvh_refit_host: invalid mesh")
+    rc = L.spray_rt_qnodes4_host(v0.ctypes.data, len(v0), f.ctypes.data, len(f), C.byref(nq),
+                                 None, None, None)
+    if rc != 0:
+        e = SprayRtError("bvh_refit_host: the built mesh cannot be quantized (%d)" % rc)
+        e.code = rc
+        raise e
+    out = {"nodes": np.zeros((nn.value, 64), np.uint8), "tris": np.zeros((len(f), 12), np.float32),
+           "grid": np.zeros(6, np.float32), "qnodes4": np.zeros((nq.value, 64), np.uint8)}
+    rc = L.spray_rt_bvh_refit_host(v0.ctypes.data, v1.ctypes.data, len(v0), f.ctypes.data, len(f),
+                                   out["nodes"].ctypes.data, out["tris"].ctypes.data,
+                                   out["grid"].ctypes.data, out["qnodes4"].ctypes.data)
+    if rc != 0:
+        e = SprayRtError("bvh_refit_host failed (%d)" % rc)
+        e.code = rc
+        raise e
+    return out
 
 
 def host_parse_scene(desc, ply_path=""):
@@ -135,8 +169,25 @@ class RtContext:
                 raise SprayRtError("spray_rt_create(%d) failed: %d" % (device, rc))
             handle = h.value
         self.h = handle
+        self._device = int(device)
+        self._nverts = {}  # slot -> vertices of its last upload_domain (refit argument checks)
+        self._children = []  # engines / caches created on this context: closed before it
+
+    def _adopt(self, child):
+        """Objects whose native handle points into this context (InsituEngine,
+        OocCache) register here: the context must outlive them, also when the
+        garbage collector finalizes an unreachable group in any order -- their
+        destroy calls read the context (its device, its stream)."""
+        self._children.append(child)
+
+    def _release(self, child):
+        kids = getattr(self, "_children", None)
+        if kids and child in kids:
+            kids.remove(child)
 
     def close(self):
+        for child in list(getattr(self, "_children", ())):
+            child.close()
         if getattr(self, "h", None) and self._own:
             lib().spray_rt_destroy(self.h)
         self.h = None
@@ -150,7 +201,9 @@ class RtContext:
     def _check(self, rc, what):
         if rc != 0:
             msg = lib().spray_rt_last_error(self.h)
-            raise SprayRtError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+            e = SprayRtError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""))
+            e.code = rc
+            raise e
 
     # ---- context ----
     def set_stream(self, stream):
@@ -178,9 +231,88 @@ class RtContext:
             self.h, int(slot), v.ctypes.data, len(v), f.ctypes.data, len(f),
             None if c is None else c.ctypes.data, None if n is None else n.ctypes.data,
             1 if async_ else 0), "domain_upload")
+        self._nverts[int(slot)] = len(v)
 
     def release_domain(self, slot):
         self._check(lib().spray_rt_domain_release(self.h, int(slot)), "domain_release")
+        self._nverts.pop(int(slot), None)
+
+    # ---- moving geometry ----
+    SLOT_NODES, SLOT_TRIS, SLOT_PRIMS, SLOT_QNODES4, SLOT_QGRID, SLOT_NORMALS = range(6)
+    _SLOT_DTYPES = (np.uint8, np.float32, np.uint32, np.uint8, np.float32, np.float32)
+
+    def refit_domains(self, slots, verts, normals=None, bounds=False):
+        """spray_rt_domains_refit: new vertex positions (and normals, for
+        slots uploaded with them) for resident slots of unchanged topology.
+        verts[i] / normals[i]: float32 [nverts, 3] numpy arrays (staged; the
+        call is synchronous) or torch tensors on the GPU (enqueued).  bounds:
+        True returns the slots' new exact boxes as a numpy [n, 6] array
+        (synchronises); a float32 [n, 6] GPU tensor is filled in place."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(verts) != n or (normals is not None and len(normals) != n):
+            e = SprayRtError("refit_domains: %d slots, %d vertex arrays, %s normal arrays"
+                             % (n, len(verts), "no" if normals is None else len(normals)))
+            e.code = -1
+            raise e
+        keep = []
+
+        def pointer(x, slot, what):
+            if x is None:
+                return None
+            if not hasattr(x, "data_ptr"):
+                x = np.ascontiguousarray(x, np.float32)
+            want = self._nverts.get(slot)
+            if want is not None and _nbytes(x) != 12 * want:
+                e = SprayRtError("refit_domains: %s of slot %d hold %d bytes, its %d vertices "
+                                 "need %d" % (what, slot, _nbytes(x), want, 12 * want))
+                e.code = -1
+                raise e
+            a, k = _addr(x)
+            keep.append(k)
+            return a
+
+        vp = (C.c_void_p * max(n, 1))(*[pointer(v, s, "vertices") for v, s in zip(verts, slots)])
+        npp = None
+        if normals is not None:
+            npp = (C.c_void_p * max(n, 1))(*[pointer(x, s, "normals")
+                                             for x, s in zip(normals, slots)])
+        sl = (C.c_int * max(n, 1))(*slots)
+        out = None
+        if bounds is True:
+            import torch
+            out = torch.empty((max(n, 1), 6), dtype=torch.float32,
+                              device="cuda:%d" % self._device)
+        elif bounds is not False and bounds is not None:
+            out = bounds
+        b, k = _addr(out)
+        self._check(lib().spray_rt_domains_refit(self.h, n, sl, vp, npp, b), "domains_refit")
+        if bounds is True:
+            self.sync()
+            return out[:n].cpu().numpy()
+        return out
+
+    def slot_export(self, slot, what):
+        """One array of a resident slot as numpy: SLOT_NODES / SLOT_QNODES4 as
+        uint8 [n, 64] (the 64-B node records), SLOT_TRIS float32 [ntris, 12],
+        SLOT_PRIMS uint32, SLOT_QGRID float32 [6], SLOT_NORMALS float32 [nverts, 3]."""
+        nb = C.c_size_t()
+        self._check(lib().spray_rt_slot_export(self.h, int(slot), int(what), None, 0,
+                                               C.byref(nb)), "slot_export")
+        out = np.zeros(nb.value, np.uint8)
+        if nb.value:
+            self._check(lib().spray_rt_slot_export(self.h, int(slot), int(what), out.ctypes.data,
+                                                   out.nbytes, C.byref(nb)), "slot_export")
+        out = out.view(self._SLOT_DTYPES[int(what)])
+        shape = {self.SLOT_NODES: (-1, 64), self.SLOT_QNODES4: (-1, 64), self.SLOT_TRIS: (-1, 12),
+                 self.SLOT_NORMALS: (-1, 3)}.get(int(what))
+        return out.reshape(shape) if shape else out
+
+    def slot_sah(self, slot):
+        """SAH cost of the slot's current BVH2 (spray_rt_slot_sah)."""
+        v = C.c_double()
+        self._check(lib().spray_rt_slot_sah(self.h, int(slot), C.byref(v)), "slot_sah")
+        return v.value
 
     def domain_bounds(self, boxes):
         b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
@@ -544,11 +676,13 @@ class OocCache:
         h = C.c_void_p()
         rt._check(lib().spray_rt_ooc_create(rt.h, int(cache_slots), C.byref(h)), "ooc_create")
         self.h = h.value
+        rt._adopt(self)
 
     def close(self):
         if getattr(self, "h", None):
             lib().spray_rt_ooc_destroy(self.h)
             self.h = None
+            self.rt._release(self)
 
     def __del__(self):
         try:
@@ -611,6 +745,9 @@ class Scene:
 
     def close(self):
         if getattr(self, "h", None):
+            rt = getattr(self, "rt", None)
+            if rt is not None:
+                rt.close()  # what was created on the scene's context goes first
             lib().spray_scene_destroy(self.h)
             self.h = None
 

@@ -311,11 +311,13 @@ class InsituEngine:
             raise ValueError("transport must be 'rccl', 'host' or 'replay'")
         rt._check(rc, "insitu_create")
         self.h = h.value
+        rt._adopt(self)  # the context closes this engine before it goes itself
 
     def close(self):
         if getattr(self, "h", None):
             lib().spray_rt_insitu_destroy(self.h)
             self.h = None
+            self.rt._release(self)
 
     def __del__(self):
         try:
