@@ -203,8 +203,9 @@ int spray_rt_qnodes4_host(const float* verts_xyz, size_t nverts, const uint32_t*
  * Deliberately left out: the images of the out-of-core cache
  * (spray_rt_ooc_set_domain; they carry no refit metadata), the scene layer's
  * domain cache (include/spray_scene.h, spray_scene.hpp: a cache miss uploads
- * the image built from the file again), and changing topology (a device
- * build).  Not for use while lanes run (they read the slot tables). */
+ * the image built from the file again).  A new triangle list is what
+ * spray_rt_domains_build below is for.  Not for use while lanes run (they read
+ * the slot tables). */
 int spray_rt_domains_refit(spray_rt_ctx_t ctx, int n, const int* slots,
                            const float* const* verts, const float* const* vnormals,
                            float* d_bounds);
@@ -216,6 +217,57 @@ int spray_rt_domains_refit(spray_rt_ctx_t ctx, int n, const int* slots,
 int spray_rt_bvh_refit_host(const float* verts0, const float* new_verts, size_t nverts,
                             const uint32_t* faces, size_t nfaces, void* nodes_out,
                             float* tris_out, float grid_out[6], void* qnodes4_out);
+/* ---- changing topology: slots built on the device ---- */
+/* New triangle lists for n slots in one batched call on the context's stream,
+ * without the host builder: verts[i] [nverts[i]][3] floats, faces[i]
+ * [nfaces[i]][3] indices, colors_rgb[i] / vnormals[i] per vertex (either array,
+ * or single entries, may be NULL).  Every array pointer may be device or host
+ * memory (host: staged, and the call returns with the work completed).  A slot
+ * may be empty or loaded; a loaded slot's image is replaced after the queued
+ * work that reads it.  d_bounds (optional, device float[n][6]) receives each
+ * slot's exact, unpadded lo.xyz hi.xyz, as in spray_rt_domains_refit; per time
+ * step: build, then spray_rt_domain_bounds, spray_rt_map_domain,
+ * spray_rt_set_owners.
+ *
+ * Afterwards the slot is a slot of spray_rt_domain_upload for every call that
+ * takes one -- the 1M streams, every scene launch, spray_rt_slot_info / _export
+ * / _sah, spray_rt_domain_release, a later spray_rt_domains_refit -- and, since
+ * closest hits are the minimum of (t, primID) and any hits a flag, every query
+ * returns the bits it returns on the uploaded slot.  The tree differs: ranges
+ * over the triangles sorted by (30-bit Morton code of the box centroid, face)
+ * split at the highest differing code bit (the median under the host builder's
+ * depth rule), nodes and QNode4s numbered level by level; it is a function of
+ * the mesh alone, and spray_rt_bvh_build_device_host restates it byte for byte.
+ * It costs more to trace than the host builder's binned-SAH tree (DESIGN.md
+ * section 11 has the figures): prefer spray_rt_domain_upload for geometry that
+ * stays, this call for geometry that is replaced every time step.  One
+ * workgroup per slot builds the topology: made for many small domains, correct
+ * but slow for one huge one.
+ *
+ * At most two host reads per call, however many slots (the sort's partition of
+ * the segments by size, and one record per slot).  A failed call leaves every
+ * slot of the call exactly as it was: SPRAY_RT_ERR_ARG for NULL arrays, a slot
+ * listed twice, nfaces >= 2^29, a face index >= nverts, or a non-finite
+ * coordinate (or edge) of a referenced vertex; SPRAY_RT_ERR_LIMIT when a box
+ * cannot be quantized.  spray_rt_last_error names the slot.  An empty mesh gives
+ * the empty slot an upload gives.  Not for use while lanes run. */
+int spray_rt_domains_build(spray_rt_ctx_t ctx, int n, const int* slots,
+                           const float* const* verts, const size_t* nverts,
+                           const uint32_t* const* faces, const size_t* nfaces,
+                           const uint32_t* const* colors_rgb, const float* const* vnormals,
+                           float* d_bounds);
+/* Host-only restatement (no GPU) of the same algorithm: the arrays
+ * spray_rt_domains_build leaves in a slot, byte for byte.  Any output may be
+ * NULL; a call with NULL outputs reports the sizes (nodes_out BvhNode[*nnodes],
+ * tris_out float[nfaces][12], prims_out uint32[nfaces], qnodes4_out
+ * QNode4[*nq]).  depth: deepest leaf (the root is depth 0); stack_bound: pending
+ * entries of the 4-wide walk; nmedian: the splits the depth rule forced to the
+ * median.  SPRAY_RT_ERR_ARG / SPRAY_RT_ERR_LIMIT as spray_rt_domains_build. */
+int spray_rt_bvh_build_device_host(const float* verts, size_t nverts, const uint32_t* faces,
+                                   size_t nfaces, size_t* nnodes, size_t* nq, int* depth,
+                                   int* stack_bound, int* nmedian, void* nodes_out,
+                                   float* tris_out, uint32_t* prims_out, float grid_out[6],
+                                   void* qnodes4_out);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes

@@ -54,6 +54,15 @@ bool quantize_nodes4(const std::vector<BvhNode>& nodes, QGrid* grid,
 void refit_order(const std::vector<BvhNode>& nodes, std::vector<uint32_t>* order,
                  uint32_t level[kRefitLevels], int* height);
 
+// The refit of a built image on the host (refit.cpp), step for step what the
+// refit kernels do: boxes, records, grid and QNode4 child boxes of `built`'s
+// topology on `verts`.  Returns the refit::kBad* bits.  exact (optional): the
+// fitted boxes before the padding -- what the device build collapses over.
+uint32_t refit_host(const BvhImage& built, const std::vector<QNode4>& q0,
+                    const std::vector<int32_t>& qsrc, const float* verts, const uint32_t* faces,
+                    std::vector<BvhNode>* nodes, std::vector<float>* tris, QGrid* grid,
+                    std::vector<QNode4>* qn, std::vector<BvhNode>* exact = nullptr);
+
 // Top-level tree over domain boxes [n][6] (lo, hi): same builder, one domain
 // per leaf (ref ~(id << 2)), EXACT union boxes (no padding) so that the
 // reference's intersectAabb evaluated on a parent accepts whenever it accepts

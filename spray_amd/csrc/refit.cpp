@@ -26,10 +26,11 @@ using namespace spray_rt;
 using namespace spray_rt::detail;
 
 namespace {
-
 const float* side_lo(const BvhNode& n, int side) { return side ? n.r_lo : n.l_lo; }
 const float* side_hi(const BvhNode& n, int side) { return side ? n.r_hi : n.l_hi; }
+}  // namespace
 
+namespace spray_rt {
 // The refit of a built image on the host, step for step what the kernels do.
 // built: the canonical BVH2 (padded boxes; only its refs, prims and empty
 // boxes are read), q0 / qsrc: its QNode4 collapse and the children's sources.
@@ -37,7 +38,7 @@ const float* side_hi(const BvhNode& n, int side) { return side ? n.r_hi : n.l_hi
 uint32_t refit_host(const BvhImage& built, const std::vector<QNode4>& q0,
                     const std::vector<int32_t>& qsrc, const float* verts, const uint32_t* faces,
                     std::vector<BvhNode>* nodes, std::vector<float>* tris, QGrid* grid,
-                    std::vector<QNode4>* qn) {
+                    std::vector<QNode4>* qn, std::vector<BvhNode>* exact) {
   uint32_t status = 0;
   const size_t nn = built.nodes.size(), nt = built.prims.size();
   tris->resize(12 * nt);
@@ -77,6 +78,7 @@ uint32_t refit_host(const BvhImage& built, const std::vector<QNode4>& q0,
       }
     }
   }
+  if (exact) *exact = ex;
   *nodes = ex;
   for (BvhNode& n : *nodes) {
     refit::pad_box(n.l_lo, n.l_hi);
@@ -115,6 +117,10 @@ uint32_t refit_host(const BvhImage& built, const std::vector<QNode4>& q0,
   }
   return status;
 }
+
+}  // namespace spray_rt
+
+namespace {
 
 int check_slot(spray_rt_ctx* c, int slot) {
   if (slot < 0 || size_t(slot) >= c->slots.size() || !c->slots[size_t(slot)].dmem)

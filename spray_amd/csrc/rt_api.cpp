@@ -71,6 +71,34 @@ int ensure(spray_rt_ctx* c, void** buf, size_t* cap, size_t bytes) {
   return SPRAY_RT_OK;
 }
 
+void layout_slot_image(SlotImage* out, size_t nnodes, size_t nfaces, size_t nverts, size_t nq,
+                       bool colors, bool normals, bool quantized) {
+  // QGrid at nodes - 32, QNode4 i at nodes - 64 - 64 (i + 1) (rt_common.h)
+  const size_t b_q = nq ? align256(64 + nq * sizeof(QNode4)) : 0;
+  size_t off = b_q;
+  auto take = [&](size_t n) {
+    const size_t o = off;
+    off += align256(n);
+    return o;
+  };
+  out->o_nodes = take(nnodes * sizeof(BvhNode));
+  out->o_tris = take(12 * nfaces * sizeof(float));
+  out->o_prims = take(nfaces * sizeof(uint32_t));
+  out->o_faces = take(3 * nfaces * sizeof(uint32_t));
+  out->o_colors = colors ? take(nverts * sizeof(uint32_t)) : SIZE_MAX;
+  out->o_normals = normals ? take(3 * nverts * sizeof(float)) : SIZE_MAX;
+  out->refit = RefitInfo{};
+  if (quantized) {
+    out->refit.offset = off;
+    out->refit.nq = uint32_t(nq);
+    take((nnodes + kRefitLevels + 4 * nq) * sizeof(uint32_t));
+  }
+  out->nbytes = std::max<size_t>(256, off);
+  out->nnodes = uint32_t(nnodes);
+  out->ntris = uint32_t(nfaces);
+  out->nverts = uint32_t(nverts);
+}
+
 const char* build_slot_image(const float* verts, size_t nverts, const uint32_t* faces,
                              size_t nfaces, const uint32_t* colors, const float* normals,
                              SlotImage* out, bool quantized) {
@@ -87,56 +115,35 @@ const char* build_slot_image(const float* verts, size_t nverts, const uint32_t* 
   if (quantized && !img.nodes.empty() && !quantize_nodes4(img.nodes, &grid, &qn, &qstack, &qsrc))
     return qstack > kQ4Stack ? "4-wide node collapse exceeds the any-hit walk's stack (kQ4Stack)"
                              : "vertex coordinates beyond the range of the quantized node grid";
-  // QGrid at nodes - 32, QNode4 i at nodes - 64 - 64 (i + 1) (rt_common.h)
-  const size_t b_q = qn.empty() ? 0 : align256(64 + qn.size() * sizeof(QNode4));
-  const size_t b_nodes = align256(img.nodes.size() * sizeof(BvhNode));
-  const size_t b_tris = align256(img.tris.size() * sizeof(float));
-  const size_t b_prims = align256(img.prims.size() * sizeof(uint32_t));
-  const size_t b_faces = align256(3 * nfaces * sizeof(uint32_t));
-  const size_t b_colors = colors ? align256(nverts * sizeof(uint32_t)) : 0;
-  const size_t b_normals = normals ? align256(3 * nverts * sizeof(float)) : 0;
   std::vector<uint32_t> order;
-  out->refit = RefitInfo{};
-  if (quantized) {
-    refit_order(img.nodes, &order, out->refit.level, &out->refit.height);
-    out->refit.nq = uint32_t(qn.size());
-  }
-  const size_t b_refit =
-      quantized ? align256((order.size() + kRefitLevels + qsrc.size()) * sizeof(uint32_t)) : 0;
-  out->bytes.assign(std::max<size_t>(256, b_q + b_nodes + b_tris + b_prims + b_faces + b_colors +
-                                              b_normals + b_refit),
-                    0);
-  out->nbytes = out->bytes.size();
+  uint32_t level[kRefitLevels] = {};
+  int height = 0;
+  if (quantized) refit_order(img.nodes, &order, level, &height);
+  layout_slot_image(out, img.nodes.size(), nfaces, nverts, qn.size(), colors != nullptr,
+                    normals != nullptr, quantized);
+  out->bytes.assign(out->nbytes, 0);
   char* host = out->bytes.data();
-  size_t off = 0;
-  auto put = [&](const void* src, size_t n, size_t padded) {
+  auto put = [&](size_t off, const void* src, size_t n) {
     if (n) std::memcpy(host + off, src, n);
-    size_t o = off;
-    off += padded;
-    return o;
   };
-  if (b_q) {
-    std::memcpy(host + b_q - sizeof(QGrid), &grid, sizeof(QGrid));
+  if (!qn.empty()) {
+    std::memcpy(host + out->o_nodes - sizeof(QGrid), &grid, sizeof(QGrid));
     for (size_t i = 0; i < qn.size(); ++i)
-      std::memcpy(host + b_q - 64 - (i + 1) * sizeof(QNode4), &qn[i], sizeof(QNode4));
-    off = b_q;
+      std::memcpy(host + out->o_nodes - 64 - (i + 1) * sizeof(QNode4), &qn[i], sizeof(QNode4));
   }
-  out->o_nodes = put(img.nodes.data(), img.nodes.size() * sizeof(BvhNode), b_nodes);
-  out->o_tris = put(img.tris.data(), img.tris.size() * sizeof(float), b_tris);
-  out->o_prims = put(img.prims.data(), img.prims.size() * sizeof(uint32_t), b_prims);
-  out->o_faces = put(faces, 3 * nfaces * sizeof(uint32_t), b_faces);
-  out->o_colors = colors ? put(colors, nverts * sizeof(uint32_t), b_colors) : SIZE_MAX;
-  out->o_normals = normals ? put(normals, 3 * nverts * sizeof(float), b_normals) : SIZE_MAX;
+  put(out->o_nodes, img.nodes.data(), img.nodes.size() * sizeof(BvhNode));
+  put(out->o_tris, img.tris.data(), img.tris.size() * sizeof(float));
+  put(out->o_prims, img.prims.data(), img.prims.size() * sizeof(uint32_t));
+  put(out->o_faces, faces, 3 * nfaces * sizeof(uint32_t));
+  if (colors) put(out->o_colors, colors, nverts * sizeof(uint32_t));
+  if (normals) put(out->o_normals, normals, 3 * nverts * sizeof(float));
   if (quantized) {
-    out->refit.offset = off;
-    if (!order.empty()) std::memcpy(host + off, order.data(), order.size() * 4);
-    std::memcpy(host + out->refit.o_level(order.size()), out->refit.level, kRefitLevels * 4);
-    if (!qsrc.empty())
-      std::memcpy(host + out->refit.o_qsrc(order.size()), qsrc.data(), qsrc.size() * 4);
+    out->refit.height = height;
+    std::memcpy(out->refit.level, level, sizeof(level));
+    put(out->refit.offset, order.data(), order.size() * 4);
+    put(out->refit.o_level(order.size()), level, kRefitLevels * 4);
+    put(out->refit.o_qsrc(order.size()), qsrc.data(), qsrc.size() * 4);
   }
-  out->nnodes = uint32_t(img.nodes.size());
-  out->ntris = uint32_t(img.prims.size());
-  out->nverts = uint32_t(nverts);
   out->depth = img.depth;
   return nullptr;
 }
@@ -384,10 +391,11 @@ int spray_rt_destroy(spray_rt_ctx_t c) {
   void* bufs[] = {c->d_slots, c->d_boxes, c->d_dom2slot, c->d_domtrav, c->d_owner, c->d_tlas, c->d_seg_slot,
                   c->d_seg_off, c->d_stage, c->d_stage2, c->d_stage3,
                   c->d_block_counts, c->d_heads, c->d_sel, c->d_bsdf, c->d_frame, c->d_fstats, c->d_ftab,
-                  c->d_refit, c->d_sah};
+                  c->d_refit, c->d_sah, c->d_build, c->d_sort};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->h_refit) (void)hipHostFree(c->h_refit);
+  if (c->h_build) (void)hipHostFree(c->h_build);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
   delete c;

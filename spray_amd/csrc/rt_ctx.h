@@ -92,6 +92,12 @@ struct spray_rt_ctx {
   void* h_refit = nullptr;  // pinned mirror of the job table and the status words
   size_t h_refit_cap = 0;
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
+  void* d_build = nullptr;  // device build: job tables, records and the scratch images
+  size_t build_cap = 0;
+  void* h_build = nullptr;  // pinned mirror of the job tables and the records
+  size_t h_build_cap = 0;
+  void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
+  size_t sort_cap = 0;
   uint32_t* d_block_counts = nullptr;
   // work-queue heads of the persistent launches: [0, kHeadsBytes) zeroed by
   // each launch, [kHeadsBytes, 2 kHeadsBytes) zeroed by a frame's launch_clear
@@ -150,6 +156,10 @@ struct SlotImage {
   // descriptor of the image once copied to device address base
   SlotDesc desc_at(const void* base) const;
 };
+// Offsets, counts and size of an image of these counts (bytes stays empty):
+// the layout build_slot_image packs and the device build commits into.
+void layout_slot_image(SlotImage* out, size_t nnodes, size_t nfaces, size_t nverts, size_t nq,
+                       bool colors, bool normals, bool quantized);
 // Builds the canonical BVH2 (bvh_build.h) and packs the image.  Returns
 // nullptr on success, else what is wrong with the mesh (face index out of
 // range, too many faces, non-finite vertex, coordinates beyond the range of

@@ -16,7 +16,7 @@ from ._native import (HIT_DTYPE, INVALID_ID, RAY_DTYPE, RTC_ISECT_DTYPE, BsdfRec
                       SprayRtError, lib)
 
 __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_rays",
-           "bvh_refit_host",
+           "bvh_refit_host", "bvh_build_device_host",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
            "HIT_DTYPE", "RTC_ISECT_DTYPE", "INVALID_ID", "SprayRtError"]
@@ -103,6 +103,35 @@ def bvh_refit_host(verts0, new_verts, faces):
         e = SprayRtError("bvh_refit_host failed (%d)" % rc)
         e.code = rc
         raise e
+    return out
+
+
+def bvh_build_device_host(verts, faces):
+    """spray_rt_bvh_build_device_host (no GPU): the image RtContext.build_domains
+    leaves in a slot -> dict of nodes (uint8 [nnodes, 64]), tris (float32
+    [ntris, 12]), prims (uint32 [ntris]), grid (float32 [6]), qnodes4 (uint8
+    [nq, 64]), depth, stack_bound, nmedian."""
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    L = lib()
+    nn, nq = C.c_size_t(), C.c_size_t()
+    depth, bound, nmed = C.c_int(), C.c_int(), C.c_int()
+
+    def call(*outs):
+        rc = L.spray_rt_bvh_build_device_host(v.ctypes.data, len(v), f.ctypes.data, len(f),
+                                              C.byref(nn), C.byref(nq), C.byref(depth),
+                                              C.byref(bound), C.byref(nmed), *outs)
+        if rc != 0:
+            e = SprayRtError("bvh_build_device_host failed (%d)" % rc)
+            e.code = rc
+            raise e
+
+    call(None, None, None, None, None)
+    out = {"nodes": np.zeros((nn.value, 64), np.uint8), "tris": np.zeros((len(f), 12), np.float32),
+           "prims": np.zeros(len(f), np.uint32), "grid": np.zeros(6, np.float32),
+           "qnodes4": np.zeros((nq.value, 64), np.uint8)}
+    call(*[out[k].ctypes.data for k in ("nodes", "tris", "prims", "grid", "qnodes4")])
+    out.update(depth=depth.value, stack_bound=bound.value, nmedian=nmed.value)
     return out
 
 
@@ -287,6 +316,73 @@ class RtContext:
             out = bounds
         b, k = _addr(out)
         self._check(lib().spray_rt_domains_refit(self.h, n, sl, vp, npp, b), "domains_refit")
+        if bounds is True:
+            self.sync()
+            return out[:n].cpu().numpy()
+        return out
+
+    def build_domains(self, slots, verts, faces, colors=None, normals=None, bounds=None):
+        """spray_rt_domains_build: new triangle lists into slots (empty or
+        loaded), the trees built on the device in one batched call.  verts[i]
+        float32 [nv, 3], faces[i] uint32 [nf, 3], colors[i] uint32 [nv],
+        normals[i] float32 [nv, 3] (the lists, or single entries, may be None):
+        numpy arrays (staged; the call is synchronous) or torch tensors on the
+        GPU (enqueued).  bounds as in refit_domains."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        for name, arr in (("vertex", verts), ("face", faces), ("color", colors),
+                          ("normal", normals)):
+            if (arr is None and name in ("vertex", "face")) or (arr is not None and len(arr) != n):
+                e = SprayRtError("build_domains: %d slots, %s %s arrays"
+                                 % (n, "no" if arr is None else len(arr), name))
+                e.code = -1
+                raise e
+        keep = []
+
+        def pointer(x, dtype):
+            if x is None:
+                return None
+            if not hasattr(x, "data_ptr"):
+                x = np.ascontiguousarray(x, dtype)
+            elif x.element_size() != 4:
+                raise TypeError("build_domains: tensors hold 32-bit elements")
+            a, k = _addr(x)
+            keep.append(k)
+            return a
+
+        def count(x, per):
+            if hasattr(x, "data_ptr"):
+                return x.numel() // per
+            return np.asarray(x).size // per
+
+        nv = [count(v, 3) for v in verts]
+        nf = [count(f, 3) for f in faces]
+        for i in range(n):
+            for name, arr, per in (("colors", colors, 1), ("normals", normals, 3)):
+                if arr is not None and arr[i] is not None and count(arr[i], per) != nv[i]:
+                    e = SprayRtError("build_domains: %s of slot %d do not match its %d vertices"
+                                     % (name, slots[i], nv[i]))
+                    e.code = -1
+                    raise e
+        m = max(n, 1)
+        vp = (C.c_void_p * m)(*[pointer(x, np.float32) for x in verts])
+        fp = (C.c_void_p * m)(*[pointer(x, np.uint32) for x in faces])
+        cp = None if colors is None else (C.c_void_p * m)(*[pointer(x, np.uint32) for x in colors])
+        npp = None if normals is None else (C.c_void_p * m)(*[pointer(x, np.float32)
+                                                               for x in normals])
+        sl = (C.c_int * m)(*slots)
+        nvp, nfp = (C.c_size_t * m)(*nv), (C.c_size_t * m)(*nf)
+        out = None
+        if bounds is True:
+            import torch
+            out = torch.empty((m, 6), dtype=torch.float32, device="cuda:%d" % self._device)
+        elif bounds is not False and bounds is not None:
+            out = bounds
+        b, k = _addr(out)
+        self._check(lib().spray_rt_domains_build(self.h, n, sl, vp, nvp, fp, nfp, cp, npp, b),
+                    "domains_build")
+        for s, k in zip(slots, nv):
+            self._nverts[s] = k
         if bounds is True:
             self.sync()
             return out[:n].cpu().numpy()
