@@ -268,6 +268,74 @@ int spray_rt_bvh_build_device_host(const float* verts, size_t nverts, const uint
                                    int* stack_bound, int* nmedian, void* nodes_out,
                                    float* tris_out, uint32_t* prims_out, float grid_out[6],
                                    void* qnodes4_out);
+/* ---- isosurfaces of scalar grids, extracted on the device ---- */
+/* One structured grid of scalars and the isovalue to contour it at. */
+typedef struct spray_rt_grid {
+  const float* values;  /* [nz][ny][nx], x fastest; device or host memory */
+  int32_t dims[3];      /* points per axis (nx, ny, nz), each >= 2 */
+  float origin[3];      /* point (i,j,k) at origin + (i,j,k) * spacing */
+  float spacing[3];     /* > 0 */
+  float isovalue;
+  uint32_t color_rgb;   /* one colour for every vertex ... */
+  int32_t has_color;    /* ... or none (spray_rt_domains_isosurface only) */
+} spray_rt_grid;
+/* The algorithm is fixed, so that the kernels and the host restatement agree
+ * byte for byte: marching tetrahedra over the Kuhn split
+ * of each cell (six tetrahedra, one per permutation of the axes in
+ * lexicographic order, each walking from the cell's corner (0,0,0) to (1,1,1));
+ * a sample is inside when f >= isovalue.  The mesh is welded and indexed:
+ * every vertex lies on a lattice edge that starts at its componentwise-smaller
+ * endpoint a and has one of 7 types (+x +y +z +xy +xz +yz +xyz), at
+ * pa + t * (pb - pa) per axis with t = (isovalue - fa) / (fb - fa), in float
+ * without contraction -- a function of the lattice edge alone, so the mesh is
+ * watertight within a grid, and two grids that share a sample plane and their
+ * origin arithmetic agree on it bit for bit.  Vertices are ordered by (point,
+ * x fastest; edge type), faces by (cell, x fastest; tetrahedron; triangle);
+ * Ng = (v0 - v1) x (v2 - v0) points toward decreasing values.  Normals are
+ * unnormalised: the negated gradient (central differences, one-sided on the
+ * grid boundary, divided by the spacing) of the edge's endpoints, interpolated
+ * with t.  A sample equal to the isovalue puts vertices on lattice points and
+ * may give zero-area triangles; they are kept (dropping them would break the
+ * numbering, and every later stage accepts them).  At most 12 triangles per
+ * cell; no atomic and no hash decides an index, two runs give the same bytes.
+ *
+ * spray_rt_isosurface extracts n grids into the caller's device buffers in one
+ * batched call on the context's stream: verts[i] float [cap_verts[i]][3],
+ * vnormals[i] the same (the array, or single entries, may be NULL), faces[i]
+ * uint32 [cap_faces[i]][3].  nverts_out / nfaces_out (host arrays, either may
+ * be NULL) are written on return: the call's one host read.  verts == NULL
+ * only counts.  A capacity that is too small gives SPRAY_RT_ERR_LIMIT with the
+ * counts reported and no buffer written.  Errors as
+ * spray_rt_domains_isosurface. */
+int spray_rt_isosurface(spray_rt_ctx_t ctx, int n, const spray_rt_grid* grids,
+                        float* const* verts, float* const* vnormals, uint32_t* const* faces,
+                        const size_t* cap_verts, const size_t* cap_faces, size_t* nverts_out,
+                        size_t* nfaces_out);
+/* Grids in, resident slots out: count, one host read, emit into context
+ * scratch grown on demand, then the device build of spray_rt_domains_build on
+ * those device arrays.  Afterwards slots[i] is a slot of spray_rt_domains_build
+ * of the extracted mesh of grids[i] (with its normals if with_normals, its
+ * colour if has_color), byte for byte, for every call that takes a slot, a
+ * later spray_rt_domains_refit included.  d_bounds as in spray_rt_domains_build;
+ * nfaces_out (optional, host size_t[n]) receives the triangle counts.
+ *
+ * At most three host reads per call, however many slots (the counts, and the
+ * build's two).  A failed call leaves every slot as it was: SPRAY_RT_ERR_ARG
+ * for a NULL pointer, dims < 2, a non-positive or non-finite spacing, a
+ * non-finite origin or isovalue, a non-finite sample, a bad slot or a slot
+ * listed twice; SPRAY_RT_ERR_LIMIT for 2^31 or more points, 2^29 or more faces,
+ * or a box that cannot be quantized.  spray_rt_last_error names the grid.  An
+ * empty surface gives the empty slot an empty upload gives.  Not for use while
+ * lanes run. */
+int spray_rt_domains_isosurface(spray_rt_ctx_t ctx, int n, const int* slots,
+                                const spray_rt_grid* grids, int with_normals, float* d_bounds,
+                                size_t* nfaces_out);
+/* Host-only restatement (no GPU; grid->values is host memory): the arrays the
+ * kernels write, byte for byte.  *nverts / *nfaces are always reported; any
+ * output may be NULL (verts_out float[*nverts][3], vnormals_out the same,
+ * faces_out uint32[*nfaces][3]). */
+int spray_rt_isosurface_host(const spray_rt_grid* grid, size_t* nverts, size_t* nfaces,
+                             float* verts_out, float* vnormals_out, uint32_t* faces_out);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes

@@ -81,6 +81,9 @@ SIGNATURES = {
     "spray_rt_bvh_refit_host": (I, [P, P, SZ, P, SZ, P, P, P, P]),
     "spray_rt_domains_build": (I, [P, I, P, P, P, P, P, P, P, P]),
     "spray_rt_bvh_build_device_host": (I, [P, SZ, P, SZ, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_isosurface": (I, [P, I, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_isosurface": (I, [P, I, P, P, I, P, P]),
+    "spray_rt_isosurface_host": (I, [P, P, P, P, P, P]),
     "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
     "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),

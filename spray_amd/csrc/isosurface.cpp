@@ -1,0 +1,421 @@
+// isosurface.cpp -- isosurfaces of scalar grids: spray_rt_isosurface,
+// spray_rt_domains_isosurface and the host-only restatement
+// spray_rt_isosurface_host (include/spray_rt.h).
+//
+// The extraction runs on the device (iso_kernels.hip) on fields that may
+// already be in HBM: a count pass, the call's one host read (the sizes), an
+// emit pass into the caller's buffers or into context scratch, from where
+// spray_rt_domains_build makes slots of the meshes.  Nothing is written to a
+// slot or a caller buffer before every check has passed (DESIGN.md,
+// "Isosurfaces").
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "iso_common.h"
+#include "iso_kernels.h"
+#include "rt_common.h"
+#include "rt_ctx.h"
+#include "spray_rt.h"
+
+using namespace spray_rt;
+using namespace spray_rt::detail;
+
+namespace {
+
+constexpr uint64_t kMaxPoints = uint64_t(1) << 31;
+constexpr uint64_t kMaxFaces = uint64_t(1) << 29;
+
+// What is wrong with a grid's description (nullptr: nothing); *code = the error.
+const char* grid_error(const spray_rt_grid& g, int* code) {
+  *code = SPRAY_RT_ERR_ARG;
+  if (!g.values) return "null values";
+  for (int a = 0; a < 3; ++a) {
+    if (g.dims[a] < 2) return "fewer than 2 points on an axis";
+    if (!(g.spacing[a] > 0.0f) || !refit::finite_f(g.spacing[a]))
+      return "spacing is not positive and finite";
+    if (!refit::finite_f(g.origin[a])) return "non-finite origin";
+  }
+  if (!refit::finite_f(g.isovalue)) return "non-finite isovalue";
+  *code = SPRAY_RT_ERR_LIMIT;
+  if (uint64_t(g.dims[0]) * uint64_t(g.dims[1]) * uint64_t(g.dims[2]) >= kMaxPoints)
+    return "2^31 or more points";
+  *code = SPRAY_RT_OK;
+  return nullptr;
+}
+
+// The samples of the cell whose minimum corner is (i, j, k).
+void load_cell(const spray_rt_grid& g, int i, int j, int k, uint32_t valid, float f[8]) {
+  const size_t nx = size_t(g.dims[0]), ny = size_t(g.dims[1]);
+  const size_t p = size_t(i) + nx * (size_t(j) + ny * size_t(k));
+  for (int c = 0; c < 8; ++c) {
+    f[c] = 0.0f;
+    if ((valid >> c) & 1u)
+      f[c] = g.values[p + size_t(c & 1) + nx * (size_t((c >> 1) & 1) + ny * size_t(c >> 2))];
+  }
+}
+
+struct HostMesh {
+  std::vector<float> verts, normals;
+  std::vector<uint32_t> faces;
+  uint64_t nverts = 0, nfaces = 0;
+};
+
+// The extraction on the host, step for step what the kernels do.
+int extract_host(const spray_rt_grid& g, bool emit, bool with_normals, HostMesh* out) {
+  int code;
+  if (grid_error(g, &code)) return code;
+  const int nx = g.dims[0], ny = g.dims[1], nz = g.dims[2];
+  const size_t np = size_t(nx) * size_t(ny) * size_t(nz);
+  // count: crossing mask and first vertex of every point, the totals
+  std::vector<uint8_t> emask(np);
+  std::vector<uint64_t> vfirst(np);
+  uint64_t nv = 0, nf = 0;
+  size_t p = 0;
+  for (int k = 0; k < nz; ++k)
+    for (int j = 0; j < ny; ++j)
+      for (int i = 0; i < nx; ++i, ++p) {
+        const uint32_t valid = iso::valid_corners(i, j, k, nx, ny, nz);
+        float f[8];
+        load_cell(g, i, j, k, valid, f);
+        if (!refit::finite_f(f[0])) return SPRAY_RT_ERR_ARG;
+        const uint32_t ins = iso::inside_mask(f, valid, g.isovalue);
+        emask[p] = uint8_t(iso::edge_mask(ins, valid));
+        vfirst[p] = nv;
+        nv += uint64_t(iso::popc(emask[p]));
+        if (valid == 0xFFu) nf += iso::cell_tri_count(ins);
+      }
+  out->nverts = nv;
+  out->nfaces = nf;
+  if (nf >= kMaxFaces || nv > UINT32_MAX) return SPRAY_RT_ERR_LIMIT;
+  if (!emit) return SPRAY_RT_OK;
+  out->verts.resize(3 * size_t(nv));
+  if (with_normals) out->normals.resize(3 * size_t(nv));
+  out->faces.resize(3 * size_t(nf));
+  size_t fid = 0;
+  p = 0;
+  for (int k = 0; k < nz; ++k)
+    for (int j = 0; j < ny; ++j)
+      for (int i = 0; i < nx; ++i, ++p) {
+        const uint32_t valid = iso::valid_corners(i, j, k, nx, ny, nz);
+        if (!emask[p] && valid != 0xFFu) continue;
+        float f[8];
+        load_cell(g, i, j, k, valid, f);
+        if (emask[p]) {
+          size_t vid = size_t(vfirst[p]);
+          float ga[3] = {0.f, 0.f, 0.f};
+          if (with_normals) iso::neg_gradient(g.values, nx, ny, nz, i, j, k, g.spacing, ga);
+          for (int type = 0; type < 7; ++type) {
+            if (!((emask[p] >> type) & 1u)) continue;
+            const int c = iso::type_corner(type);
+            const float t = iso::edge_t(f[0], f[c], g.isovalue);
+            iso::edge_vertex(g.origin, g.spacing, i, j, k, type, t, &out->verts[3 * vid]);
+            if (with_normals) {
+              float gb[3];
+              iso::neg_gradient(g.values, nx, ny, nz, i + (c & 1), j + ((c >> 1) & 1),
+                                k + (c >> 2), g.spacing, gb);
+              for (int ax = 0; ax < 3; ++ax)
+                out->normals[3 * vid + size_t(ax)] = iso::lerp(ga[ax], gb[ax], t);
+            }
+            ++vid;
+          }
+        }
+        if (valid != 0xFFu) continue;
+        const uint32_t ins = iso::inside_mask(f, valid, g.isovalue);
+        if (ins == 0 || ins == 0xFFu) continue;
+        for (int tet = 0; tet < 6; ++tet) {
+          int T[4];
+          iso::tet_corners(tet, T);
+          uint8_t e[2][3];
+          const int nt = iso::tet_triangles(iso::tet_signs(T, ins), iso::tet_odd(tet), e);
+          for (int n = 0; n < nt; ++n, ++fid)
+            for (int v = 0; v < 3; ++v) {
+              const int cu = T[e[n][v] >> 2], cv = T[e[n][v] & 3];
+              const size_t q = p + size_t(cu & 1) +
+                               size_t(nx) * (size_t((cu >> 1) & 1) + size_t(ny) * size_t(cu >> 2));
+              const int type = iso::diff_type(cu ^ cv);
+              out->faces[3 * fid + size_t(v)] =
+                  uint32_t(vfirst[q]) + uint32_t(iso::popc(emask[q] & ((1u << type) - 1u)));
+            }
+        }
+      }
+  return SPRAY_RT_OK;
+}
+
+// ---- the device extraction: count, the host read, emit ----
+
+struct IsoCall {
+  size_t o_jobs = 0, o_status = 0, o_rec = 0, o_outs = 0, head_bytes = 0;
+  uint32_t max_blocks = 0;
+  bool staged = false;  // some field came from host memory
+  std::vector<IsoRec> rec;
+};
+
+// Validates the grids, runs the count pass and the scan and reads the sizes
+// (the host read).  Messages name the grid, and its slot where slots is given.
+int iso_count(spray_rt_ctx* c, int n, const spray_rt_grid* grids, const int* slots, IsoCall* call) {
+  const size_t nj = size_t(n);
+  auto name = [&](int i) {
+    char buf[64];
+    if (slots)
+      snprintf(buf, sizeof(buf), "isosurface (grid %d, slot %d)", i, slots[i]);
+    else
+      snprintf(buf, sizeof(buf), "isosurface (grid %d)", i);
+    return std::string(buf);
+  };
+  if (n > 65535) return fail(c, SPRAY_RT_ERR_LIMIT, "isosurface: more than 65535 grids in one call");
+  for (int i = 0; i < n; ++i) {
+    int code;
+    if (const char* why = grid_error(grids[i], &code)) return fail(c, code, "%s: %s", name(i).c_str(), why);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = stream_of(c);
+
+  // ---- layout: tables (mirrored in pinned memory), then fields and scratch ----
+  call->o_jobs = 0;
+  call->o_status = call->o_jobs + align256(nj * sizeof(IsoJob));
+  call->o_rec = call->o_status + align256(nj * sizeof(uint32_t));
+  call->o_outs = call->o_rec + align256(nj * sizeof(IsoRec));
+  call->head_bytes = call->o_outs + align256(nj * sizeof(IsoOut));
+  size_t total = call->head_bytes;
+  auto take = [&](size_t bytes) {
+    const size_t o = total;
+    total += align256(bytes);
+    return o;
+  };
+  struct Scratch {
+    size_t values = SIZE_MAX, code, vblock, fblock;
+    uint32_t npoints, nblocks;
+  };
+  std::vector<Scratch> sk(nj);
+  for (int i = 0; i < n; ++i) {
+    const spray_rt_grid& g = grids[i];
+    Scratch& k = sk[size_t(i)];
+    k.npoints = uint32_t(g.dims[0]) * uint32_t(g.dims[1]) * uint32_t(g.dims[2]);
+    k.nblocks = (k.npoints + iso::kIsoBlock - 1) / iso::kIsoBlock;
+    if (!is_device_ptr(g.values)) {
+      k.values = take(size_t(k.npoints) * sizeof(float));
+      call->staged = true;
+    }
+    k.code = take(size_t(k.npoints) * sizeof(uint32_t));
+    k.vblock = take(size_t(k.nblocks) * sizeof(uint32_t));
+    k.fblock = take(size_t(k.nblocks) * sizeof(uint32_t));
+    call->max_blocks = std::max(call->max_blocks, k.nblocks);
+  }
+  {
+    const int r = ensure(c, &c->d_iso, &c->iso_cap, total);
+    if (r) return r;
+  }
+  if (c->h_iso_cap < call->head_bytes) {
+    if (c->h_iso) HIPCHK(c, hipHostFree(c->h_iso));
+    c->h_iso = nullptr;
+    c->h_iso_cap = 0;
+    const size_t want = std::max(call->head_bytes, size_t(1) << 16);
+    HIPCHK(c, hipHostMalloc(&c->h_iso, want, hipHostMallocDefault));
+    c->h_iso_cap = want;
+  }
+  char* d = static_cast<char*>(c->d_iso);
+  char* h = static_cast<char*>(c->h_iso);
+  IsoJob* jobs = reinterpret_cast<IsoJob*>(h + call->o_jobs);
+  uint32_t* h_status = reinterpret_cast<uint32_t*>(h + call->o_status);
+  for (int i = 0; i < n; ++i) {
+    const spray_rt_grid& g = grids[i];
+    const Scratch& k = sk[size_t(i)];
+    IsoJob J{};
+    J.values = g.values;
+    if (k.values != SIZE_MAX) {
+      J.values = reinterpret_cast<const float*>(d + k.values);
+      HIPCHK(c, hipMemcpyAsync(d + k.values, g.values, size_t(k.npoints) * sizeof(float),
+                               hipMemcpyHostToDevice, s));
+    }
+    J.code = reinterpret_cast<uint32_t*>(d + k.code);
+    J.vblock = reinterpret_cast<uint32_t*>(d + k.vblock);
+    J.fblock = reinterpret_cast<uint32_t*>(d + k.fblock);
+    J.rec = reinterpret_cast<IsoRec*>(d + call->o_rec) + i;
+    J.nx = g.dims[0];
+    J.ny = g.dims[1];
+    J.nz = g.dims[2];
+    J.npoints = k.npoints;
+    J.nblocks = k.nblocks;
+    for (int a = 0; a < 3; ++a) {
+      J.origin[a] = g.origin[a];
+      J.spacing[a] = g.spacing[a];
+    }
+    J.isovalue = g.isovalue;
+    J.color = g.color_rgb;
+    jobs[i] = J;
+    h_status[i] = 0;
+  }
+  HIPCHK(c, hipMemcpyAsync(d, h, call->o_rec, hipMemcpyHostToDevice, s));
+  const IsoJob* d_jobs = reinterpret_cast<const IsoJob*>(d + call->o_jobs);
+  HIPCHK(c, launch_iso_count(s, d_jobs, n, call->max_blocks,
+                             reinterpret_cast<uint32_t*>(d + call->o_status)));
+  HIPCHK(c, launch_iso_scan(s, d_jobs, n));
+  HIPCHK(c, hipMemcpyAsync(h + call->o_status, d + call->o_status, call->o_outs - call->o_status,
+                           hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));  // the sizes: the extraction's host read
+  const IsoRec* h_rec = reinterpret_cast<const IsoRec*>(h + call->o_rec);
+  call->rec.assign(h_rec, h_rec + n);
+  for (int i = 0; i < n; ++i) {
+    if (h_status[i] & iso::kBadSample)
+      return fail(c, SPRAY_RT_ERR_ARG, "%s: non-finite sample", name(i).c_str());
+    if (h_rec[i].nfaces >= kMaxFaces || h_rec[i].nverts > UINT32_MAX)
+      return fail(c, SPRAY_RT_ERR_LIMIT, "%s: 2^29 or more faces", name(i).c_str());
+  }
+  return SPRAY_RT_OK;
+}
+
+// The emit pass of a counted call into outs[n].
+int iso_emit(spray_rt_ctx* c, int n, const IsoCall& call, const std::vector<IsoOut>& outs) {
+  hipStream_t s = stream_of(c);
+  char* d = static_cast<char*>(c->d_iso);
+  char* h = static_cast<char*>(c->h_iso);
+  std::memcpy(h + call.o_outs, outs.data(), size_t(n) * sizeof(IsoOut));
+  HIPCHK(c, hipMemcpyAsync(d + call.o_outs, h + call.o_outs, size_t(n) * sizeof(IsoOut),
+                           hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipStreamSynchronize(s));  // the pinned tables are free for the next call
+  HIPCHK(c, launch_iso_emit(s, reinterpret_cast<const IsoJob*>(d + call.o_jobs),
+                            reinterpret_cast<const IsoOut*>(d + call.o_outs), n, call.max_blocks));
+  return SPRAY_RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int spray_rt_isosurface_host(const spray_rt_grid* grid, size_t* nverts, size_t* nfaces,
+                             float* verts_out, float* vnormals_out, uint32_t* faces_out) {
+  if (!grid) return SPRAY_RT_ERR_ARG;
+  HostMesh m;
+  const bool emit = verts_out || vnormals_out || faces_out;
+  const int r = extract_host(*grid, emit, vnormals_out != nullptr, &m);
+  if (nverts) *nverts = size_t(m.nverts);
+  if (nfaces) *nfaces = size_t(m.nfaces);
+  if (r) return r;
+  if (verts_out) std::memcpy(verts_out, m.verts.data(), m.verts.size() * sizeof(float));
+  if (vnormals_out) std::memcpy(vnormals_out, m.normals.data(), m.normals.size() * sizeof(float));
+  if (faces_out) std::memcpy(faces_out, m.faces.data(), m.faces.size() * sizeof(uint32_t));
+  return SPRAY_RT_OK;
+}
+
+int spray_rt_isosurface(spray_rt_ctx_t c, int n, const spray_rt_grid* grids, float* const* verts,
+                        float* const* vnormals, uint32_t* const* faces, const size_t* cap_verts,
+                        const size_t* cap_faces, size_t* nverts_out, size_t* nfaces_out) {
+  if (!c) return SPRAY_RT_ERR_ARG;
+  if (n < 0 || (n && !grids) || (n && verts && (!faces || !cap_verts || !cap_faces)))
+    return fail(c, SPRAY_RT_ERR_ARG, "isosurface: null arguments");
+  if (n == 0) return SPRAY_RT_OK;
+  IsoCall call;
+  const int r = iso_count(c, n, grids, nullptr, &call);
+  if (r) return r;
+  for (int i = 0; i < n; ++i) {
+    if (nverts_out) nverts_out[i] = size_t(call.rec[size_t(i)].nverts);
+    if (nfaces_out) nfaces_out[i] = size_t(call.rec[size_t(i)].nfaces);
+  }
+  if (!verts) return SPRAY_RT_OK;
+  std::vector<IsoOut> outs(size_t(n), IsoOut{});
+  for (int i = 0; i < n; ++i) {
+    const IsoRec& rec = call.rec[size_t(i)];
+    if (rec.nverts > cap_verts[i] || rec.nfaces > cap_faces[i])
+      return fail(c, SPRAY_RT_ERR_LIMIT,
+                  "isosurface (grid %d): %llu vertices and %llu faces do not fit the buffers", i,
+                  static_cast<unsigned long long>(rec.nverts),
+                  static_cast<unsigned long long>(rec.nfaces));
+    if ((rec.nverts && !verts[i]) || (rec.nfaces && !faces[i]))
+      return fail(c, SPRAY_RT_ERR_ARG, "isosurface (grid %d): null output buffers", i);
+    IsoOut& O = outs[size_t(i)];
+    O.verts = verts[i];
+    O.normals = vnormals ? vnormals[i] : nullptr;
+    O.faces = faces[i];
+    O.cap_verts = rec.nverts;
+    O.cap_faces = rec.nfaces;
+  }
+  const int e = iso_emit(c, n, call, outs);
+  if (e) return e;
+  if (call.staged) HIPCHK(c, hipStreamSynchronize(stream_of(c)));  // host fields: done on return
+  return SPRAY_RT_OK;
+}
+
+int spray_rt_domains_isosurface(spray_rt_ctx_t c, int n, const int* slots,
+                                const spray_rt_grid* grids, int with_normals, float* d_bounds,
+                                size_t* nfaces_out) {
+  if (!c) return SPRAY_RT_ERR_ARG;
+  if (n < 0 || (n && (!slots || !grids)))
+    return fail(c, SPRAY_RT_ERR_ARG, "isosurface: null arguments");
+  if (n == 0) return SPRAY_RT_OK;
+  const size_t nj = size_t(n);
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] > 1 << 20)
+      return fail(c, SPRAY_RT_ERR_ARG, "isosurface (grid %d): bad slot %d", i, slots[i]);
+    for (int k = 0; k < i; ++k)
+      if (slots[k] == slots[i])
+        return fail(c, SPRAY_RT_ERR_ARG, "isosurface (grid %d): slot %d listed twice", i, slots[i]);
+  }
+  IsoCall call;
+  int r = iso_count(c, n, grids, slots, &call);
+  if (r) return r;
+
+  // ---- the meshes: context scratch, sized by the counts ----
+  std::vector<size_t> o_verts(nj), o_normals(nj), o_colors(nj), o_faces(nj), nv(nj), nf(nj);
+  size_t total = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = total;
+    total += align256(bytes);
+    return o;
+  };
+  for (int i = 0; i < n; ++i) {
+    const size_t k = size_t(i);
+    nv[k] = size_t(call.rec[k].nverts);
+    nf[k] = size_t(call.rec[k].nfaces);
+    o_verts[k] = take(3 * nv[k] * sizeof(float));
+    o_normals[k] = with_normals ? take(3 * nv[k] * sizeof(float)) : SIZE_MAX;
+    o_colors[k] = grids[i].has_color ? take(nv[k] * sizeof(uint32_t)) : SIZE_MAX;
+    o_faces[k] = take(3 * nf[k] * sizeof(uint32_t));
+  }
+  r = ensure(c, &c->d_isomesh, &c->isomesh_cap, std::max<size_t>(total, 256));
+  if (r) return r;
+  char* m = static_cast<char*>(c->d_isomesh);
+  std::vector<IsoOut> outs(nj, IsoOut{});
+  std::vector<const float*> pv(nj), pn(nj);
+  std::vector<const uint32_t*> pc(nj), pf(nj);
+  for (size_t k = 0; k < nj; ++k) {
+    IsoOut& O = outs[k];
+    O.verts = reinterpret_cast<float*>(m + o_verts[k]);
+    O.normals = o_normals[k] == SIZE_MAX ? nullptr : reinterpret_cast<float*>(m + o_normals[k]);
+    O.colors = o_colors[k] == SIZE_MAX ? nullptr : reinterpret_cast<uint32_t*>(m + o_colors[k]);
+    O.faces = reinterpret_cast<uint32_t*>(m + o_faces[k]);
+    O.cap_verts = nv[k];
+    O.cap_faces = nf[k];
+    pv[k] = O.verts;
+    pn[k] = O.normals;
+    pc[k] = O.colors;
+    pf[k] = O.faces;
+  }
+  r = iso_emit(c, n, call, outs);
+  if (r) return r;
+
+  // ---- the slots: the device build on the extracted arrays ----
+  r = spray_rt_domains_build(c, n, slots, pv.data(), nv.data(), pf.data(), nf.data(), pc.data(),
+                             pn.data(), d_bounds);
+  if (r) {  // the build names the slot; name the grid as well
+    const std::string msg = c->err;
+    int slot = -1, grid = -1;
+    const size_t at = msg.find("slot ");
+    if (at != std::string::npos && sscanf(msg.c_str() + at, "slot %d", &slot) == 1)
+      for (int i = 0; i < n; ++i)
+        if (slots[i] == slot) grid = i;
+    if (grid >= 0) return fail(c, r, "isosurface (grid %d, slot %d): %s", grid, slot, msg.c_str());
+    return fail(c, r, "isosurface: %s", msg.c_str());
+  }
+  if (nfaces_out)
+    for (size_t k = 0; k < nj; ++k) nfaces_out[k] = nf[k];
+  if (call.staged) HIPCHK(c, hipStreamSynchronize(stream_of(c)));  // host fields: done on return
+  return SPRAY_RT_OK;
+}
+
+}  // extern "C"

@@ -98,6 +98,12 @@ struct spray_rt_ctx {
   size_t h_build_cap = 0;
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;
+  void* d_iso = nullptr;  // isosurface: job tables, records, staged fields, per-point scratch
+  size_t iso_cap = 0;
+  void* h_iso = nullptr;  // pinned mirror of the job tables and the records
+  size_t h_iso_cap = 0;
+  void* d_isomesh = nullptr;  // isosurface into slots: the extracted meshes
+  size_t isomesh_cap = 0;
   uint32_t* d_block_counts = nullptr;
   // work-queue heads of the persistent launches: [0, kHeadsBytes) zeroed by
   // each launch, [kHeadsBytes, 2 kHeadsBytes) zeroed by a frame's launch_clear

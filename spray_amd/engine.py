@@ -16,7 +16,7 @@ from ._native import (HIT_DTYPE, INVALID_ID, RAY_DTYPE, RTC_ISECT_DTYPE, BsdfRec
                       SprayRtError, lib)
 
 __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_rays",
-           "bvh_refit_host", "bvh_build_device_host",
+           "bvh_refit_host", "bvh_build_device_host", "isosurface_host",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
            "HIT_DTYPE", "RTC_ISECT_DTYPE", "INVALID_ID", "SprayRtError"]
@@ -133,6 +133,70 @@ def bvh_build_device_host(verts, faces):
     call(*[out[k].ctypes.data for k in ("nodes", "tris", "prims", "grid", "qnodes4")])
     out.update(depth=depth.value, stack_bound=bound.value, nmedian=nmed.value)
     return out
+
+
+class _Grid(C.Structure):
+    """spray_rt_grid."""
+    _fields_ = [("values", C.c_void_p), ("dims", C.c_int32 * 3), ("origin", C.c_float * 3),
+                ("spacing", C.c_float * 3), ("isovalue", C.c_float), ("color_rgb", C.c_uint32),
+                ("has_color", C.c_int32)]
+
+
+assert C.sizeof(_Grid) == 56
+
+
+def _grid_table(grids):
+    """[(values, origin, spacing, iso[, color])] or dicts with those keys ->
+    (spray_rt_grid array, keepalive).  values: float32 [nz, ny, nx], a numpy
+    array or a torch tensor on the GPU."""
+    arr = (_Grid * max(len(grids), 1))()
+    keep = []
+    for g, rec in zip(grids, arr):
+        if isinstance(g, dict):
+            g = (g["values"], g["origin"], g["spacing"], g["iso"], g.get("color"))
+        values, origin, spacing, iso = g[:4]
+        color = g[4] if len(g) > 4 else None
+        if hasattr(values, "data_ptr"):
+            if values.element_size() != 4 or not values.is_floating_point():
+                raise TypeError("isosurface: fields are float32")
+        else:
+            values = np.ascontiguousarray(values, np.float32)
+        if len(values.shape) != 3:
+            raise ValueError("isosurface: a field is a [nz, ny, nx] array")
+        a, k = _addr(values)
+        keep.append(k)
+        rec.values = a
+        nz, ny, nx = (int(d) for d in values.shape)
+        rec.dims = (C.c_int32 * 3)(nx, ny, nz)
+        rec.origin = (C.c_float * 3)(*[float(x) for x in origin])
+        rec.spacing = (C.c_float * 3)(*[float(x) for x in spacing])
+        rec.isovalue = float(iso)
+        rec.has_color = 0 if color is None else 1
+        rec.color_rgb = 0 if color is None else int(color)
+    return arr, keep
+
+
+def isosurface_host(values, origin, spacing, iso, normals=True):
+    """spray_rt_isosurface_host (no GPU): the mesh RtContext.isosurface extracts
+    from a float32 [nz, ny, nx] field -> (verts float32 [nv, 3], normals float32
+    [nv, 3] or None, faces uint32 [nf, 3])."""
+    arr, keep = _grid_table([(np.ascontiguousarray(values, np.float32), origin, spacing, iso)])
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_isosurface_host(C.addressof(arr), C.byref(nv), C.byref(nf), *outs)
+        if rc != 0:
+            e = SprayRtError("isosurface_host failed (%d)" % rc)
+            e.code = rc
+            raise e
+
+    call(None, None, None)
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals else None
+    f = np.zeros((nf.value, 3), np.uint32)
+    call(v.ctypes.data, None if n is None else n.ctypes.data, f.ctypes.data)
+    return v, n, f
 
 
 def host_parse_scene(desc, ply_path=""):
@@ -383,6 +447,75 @@ class RtContext:
                     "domains_build")
         for s, k in zip(slots, nv):
             self._nverts[s] = k
+        if bounds is True:
+            self.sync()
+            return out[:n].cpu().numpy()
+        return out
+
+    # ---- isosurfaces ----
+    def isosurface(self, grids, normals=True, capacity=None):
+        """spray_rt_isosurface: the isosurfaces of grids (see _grid_table) in one
+        batched call -> [(verts float32 [nv, 3], normals float32 [nv, 3] or
+        None, faces int32 [nf, 3] holding the uint32 bits)] as GPU tensors of
+        the exact sizes (a counting call first).  capacity=(nverts, nfaces)
+        skips the counting call and extracts into buffers of that size per
+        grid (SPRAY_RT_ERR_LIMIT if one is too small)."""
+        import torch
+        n = len(grids)
+        arr, keep = _grid_table(grids)
+        m = max(n, 1)
+        nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        if capacity is None:
+            self._check(lib().spray_rt_isosurface(self.h, n, arr, None, None, None, None, None,
+                                                  nv, nf), "isosurface")
+            caps = [(nv[i], nf[i]) for i in range(n)]
+        else:
+            caps = [(int(capacity[0]), int(capacity[1]))] * n
+        dev = "cuda:%d" % self._device
+        # zeroed, one element at least: a buffer a failed call must not touch
+        v = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) for cv, _ in caps]
+        nr = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) if normals else None
+              for cv, _ in caps]
+        f = [torch.zeros((max(cf, 1), 3), dtype=torch.int32, device=dev) for _, cf in caps]
+        ptrs = lambda xs: (C.c_void_p * m)(*[None if x is None else x.data_ptr() for x in xs])
+        try:
+            self._check(lib().spray_rt_isosurface(
+                self.h, n, arr, ptrs(v), ptrs(nr) if normals else None, ptrs(f),
+                (C.c_size_t * m)(*[c[0] for c in caps]), (C.c_size_t * m)(*[c[1] for c in caps]),
+                nv, nf), "isosurface")
+        except SprayRtError as e:
+            e.counts = [(nv[i], nf[i]) for i in range(n)]
+            e.buffers = (v, nr, f)
+            raise
+        return [(v[i][:nv[i]], nr[i][:nv[i]] if normals else None, f[i][:nf[i]])
+                for i in range(n)]
+
+    def isosurface_domains(self, slots, grids, normals=True, bounds=None):
+        """spray_rt_domains_isosurface: the isosurfaces of grids (see
+        _grid_table; a grid's optional colour is every vertex's) into slots
+        (empty or loaded), extracted and built on the device.  bounds as in
+        refit_domains; slot_info(slot)["tris"] has the triangle counts."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(grids) != n:
+            e = SprayRtError("isosurface_domains: %d slots, %d grids" % (n, len(grids)))
+            e.code = -1
+            raise e
+        arr, keep = _grid_table(grids)
+        m = max(n, 1)
+        sl = (C.c_int * m)(*slots)
+        out = None
+        if bounds is True:
+            import torch
+            out = torch.empty((m, 6), dtype=torch.float32, device="cuda:%d" % self._device)
+        elif bounds is not False and bounds is not None:
+            out = bounds
+        b, k = _addr(out)
+        nf = (C.c_size_t * m)()
+        self._check(lib().spray_rt_domains_isosurface(self.h, n, sl, arr, 1 if normals else 0, b,
+                                                      nf), "domains_isosurface")
+        for s in slots:
+            self._nverts.pop(s, None)  # the vertex count is the extraction's
         if bounds is True:
             self.sync()
             return out[:n].cpu().numpy()
