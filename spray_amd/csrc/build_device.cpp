@@ -177,13 +177,6 @@ int build_host(const float* verts, size_t nverts, const uint32_t* faces, size_t 
   return SPRAY_RT_OK;
 }
 
-size_t align_up(size_t x) { return align256(x); }
-
-struct Staged {  // one caller array: where the kernels read it
-  const void* dev = nullptr;
-  size_t stage = SIZE_MAX;  // offset into d_stage (host arrays)
-};
-
 }  // namespace
 
 extern "C" {
@@ -213,11 +206,21 @@ int spray_rt_bvh_build_device_host(const float* verts, size_t nverts, const uint
   return SPRAY_RT_OK;
 }
 
-int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const float* const* verts,
-                           const size_t* nverts, const uint32_t* const* faces,
-                           const size_t* nfaces, const uint32_t* const* colors_rgb,
-                           const float* const* vnormals, float* d_bounds) {
-  if (!c) return SPRAY_RT_ERR_ARG;
+}  // extern "C"
+
+namespace spray_rt {
+namespace detail {
+
+int domains_build(spray_rt_ctx* c, int n, const int* slots, const float* const* verts,
+                  const size_t* nverts, const uint32_t* const* faces, const size_t* nfaces,
+                  const uint32_t* const* colors_rgb, const float* const* vnormals,
+                  float* d_bounds, int* failed_job) {
+  *failed_job = -1;
+  // a failure that names job i's slot
+  auto fail_job = [&](int i, int code, const char* fmt, auto... args) {
+    *failed_job = i;
+    return fail(c, code, fmt, args...);
+  };
   if (n < 0 || (n && (!slots || !verts || !nverts || !faces || !nfaces)))
     return fail(c, SPRAY_RT_ERR_ARG, "build: null arguments");
   if (n == 0) return SPRAY_RT_OK;
@@ -226,18 +229,18 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
   uint64_t total_tris = 0;
   for (int i = 0; i < n; ++i) {
     if (slots[i] < 0 || slots[i] > 1 << 20)
-      return fail(c, SPRAY_RT_ERR_ARG, "build: bad slot %d", slots[i]);
+      return fail_job(i, SPRAY_RT_ERR_ARG, "build: bad slot %d", slots[i]);
     for (int k = 0; k < i; ++k)
       if (slots[k] == slots[i])
-        return fail(c, SPRAY_RT_ERR_ARG, "build: slot %d listed twice", slots[i]);
+        return fail_job(i, SPRAY_RT_ERR_ARG, "build: slot %d listed twice", slots[i]);
     if ((nverts[i] && !verts[i]) || (nfaces[i] && !faces[i]))
-      return fail(c, SPRAY_RT_ERR_ARG, "build (slot %d): null mesh arrays", slots[i]);
+      return fail_job(i, SPRAY_RT_ERR_ARG, "build (slot %d): null mesh arrays", slots[i]);
     if (nfaces[i] >= (size_t(1) << 29))
-      return fail(c, SPRAY_RT_ERR_ARG, "build (slot %d): mesh too large (>= 2^29 faces)", slots[i]);
+      return fail_job(i, SPRAY_RT_ERR_ARG, "build (slot %d): mesh too large (>= 2^29 faces)", slots[i]);
     if (nverts[i] > UINT32_MAX)
-      return fail(c, SPRAY_RT_ERR_ARG, "build (slot %d): too many vertices", slots[i]);
+      return fail_job(i, SPRAY_RT_ERR_ARG, "build (slot %d): too many vertices", slots[i]);
     if (nfaces[i] && !nverts[i])
-      return fail(c, SPRAY_RT_ERR_ARG, "build (slot %d): face index out of range", slots[i]);
+      return fail_job(i, SPRAY_RT_ERR_ARG, "build (slot %d): face index out of range", slots[i]);
     total_tris += nfaces[i];
   }
   if (total_tris > UINT32_MAX)
@@ -246,122 +249,94 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
   hipStream_t s = stream_of(c);
 
   // ---- caller arrays: device pointers as they are, host arrays staged ----
-  std::vector<Staged> sv(nj), sf(nj), sc(nj), sn(nj);
-  size_t stage_bytes = 0;
-  auto place = [&](Staged* st, const void* p, size_t bytes) {
-    if (!p || !bytes) return;
-    if (is_device_ptr(p)) {
-      st->dev = p;
-    } else {
-      st->stage = stage_bytes;
-      stage_bytes += align_up(bytes);
-    }
-  };
+  Stager stage;  // items 4 i + kVerts .. kNormals: job i's arrays
+  enum { kVerts, kFaces, kColors, kNormals };
+  auto colors_of = [&](int i) { return stage.dev<uint32_t>(4 * size_t(i) + kColors); };
+  auto normals_of = [&](int i) { return stage.dev<float>(4 * size_t(i) + kNormals); };
   for (int i = 0; i < n; ++i) {
-    place(&sv[size_t(i)], verts[i], 3 * nverts[i] * sizeof(float));
-    place(&sf[size_t(i)], faces[i], 3 * nfaces[i] * sizeof(uint32_t));
-    place(&sc[size_t(i)], colors_rgb ? colors_rgb[i] : nullptr, nverts[i] * sizeof(uint32_t));
-    place(&sn[size_t(i)], vnormals ? vnormals[i] : nullptr, 3 * nverts[i] * sizeof(float));
+    stage.place(verts[i], 3 * nverts[i] * sizeof(float));
+    stage.place(faces[i], 3 * nfaces[i] * sizeof(uint32_t));
+    stage.place(colors_rgb ? colors_rgb[i] : nullptr, nverts[i] * sizeof(uint32_t));
+    stage.place(vnormals ? vnormals[i] : nullptr, 3 * nverts[i] * sizeof(float));
   }
-  if (stage_bytes) {
-    const int r = ensure(c, &c->d_stage, &c->stage_cap, stage_bytes);
-    if (r) return r;
-    auto stage = [&](Staged* st, const void* p, size_t bytes) -> hipError_t {
-      if (st->stage == SIZE_MAX) return hipSuccess;
-      char* dst = static_cast<char*>(c->d_stage) + st->stage;
-      st->dev = dst;
-      return hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s);
-    };
-    for (int i = 0; i < n; ++i) {
-      HIPCHK(c, stage(&sv[size_t(i)], verts[i], 3 * nverts[i] * sizeof(float)));
-      HIPCHK(c, stage(&sf[size_t(i)], faces[i], 3 * nfaces[i] * sizeof(uint32_t)));
-      HIPCHK(c, stage(&sc[size_t(i)], colors_rgb ? colors_rgb[i] : nullptr,
-                      nverts[i] * sizeof(uint32_t)));
-      HIPCHK(c, stage(&sn[size_t(i)], vnormals ? vnormals[i] : nullptr,
-                      3 * nverts[i] * sizeof(float)));
-    }
+  if (stage.any) {
+    if (const int r = ensure(c, &c->d_stage, &c->stage_cap, stage.own.used)) return r;
+    HIPCHK(c, stage.copy(c->d_stage, s));
   }
 
   // ---- layout of the scratch: tables (mirrored in pinned memory), then arrays ----
-  const size_t o_bjobs = 0;
-  const size_t o_rjobs = o_bjobs + align_up(nj * sizeof(BuildJob));
-  const size_t o_offsets = o_rjobs + align_up(nj * sizeof(RefitJob));
-  const size_t o_status = o_offsets + align_up((nj + 1) * sizeof(uint32_t));
-  const size_t o_rec = o_status + align_up(nj * sizeof(uint32_t));
-  const size_t o_jobs2 = o_rec + align_up(nj * sizeof(BuildRec));
-  const size_t o_copies = o_jobs2 + align_up(nj * sizeof(RefitJob));
-  const size_t head_bytes = o_copies + align_up(6 * nj * sizeof(CopyJob));
-  const size_t o_grid = head_bytes;
-  const size_t o_keys = o_grid + align_up(nj * sizeof(QGrid));
-  const size_t o_sorted = o_keys + align_up(size_t(total_tris) * sizeof(uint64_t));
-  size_t total = o_sorted + align_up(size_t(total_tris) * sizeof(uint64_t));
+  JobArena& A = c->build;
+  A.reset();
+  const auto t_bjobs = A.take_head<BuildJob>(nj);
+  const auto t_rjobs = A.take_head<RefitJob>(nj);
+  const auto t_offsets = A.take_head<uint32_t>(nj + 1);
+  // phase 1 uploads [0, m_rec) and reads back [m_status, m_jobs2); phase 2
+  // uploads [m_jobs2, head)
+  const size_t m_status = A.mark();
+  const auto t_status = A.take_head<uint32_t>(nj);
+  const size_t m_rec = A.mark();
+  const auto t_rec = A.take_head<BuildRec>(nj);
+  const size_t m_jobs2 = A.mark();
+  const auto t_jobs2 = A.take_head<RefitJob>(nj);
+  const auto t_copies = A.take_head<CopyJob>(6 * nj);
+  const auto t_grid = A.take<QGrid>(nj);
+  const auto t_keys = A.take<uint64_t>(size_t(total_tris));
+  const auto t_sorted = A.take<uint64_t>(size_t(total_tris));
   struct Scratch {
-    size_t part, prims, qfront, nodes, sq, range, qlist, hgt, order, level, qsrc;
+    Take<float> part;
+    Take<uint32_t> prims, order, level;
+    Take<BvhNode> nodes;
+    Take<QNode4> sq;
+    Take<uint2> range, qlist;
+    Take<uint8_t> hgt;
+    Take<int32_t> qsrc;
     uint32_t cap;
   };
   std::vector<Scratch> sk(nj);
-  auto take = [&](size_t bytes) {
-    const size_t o = total;
-    total += align_up(bytes);
-    return o;
-  };
   uint32_t max_tris = 0, max_verts = 0, max_cap = 0;
   for (int i = 0; i < n; ++i) {
     Scratch& k = sk[size_t(i)];
     const uint32_t nt = uint32_t(nfaces[i]);
     k.cap = nt > 1 ? nt - 1 : 1;
-    k.part = take(size_t(kBuildParts) * 6 * sizeof(float));
-    k.prims = take(size_t(nt) * sizeof(uint32_t));
-    k.qfront = take(64 + size_t(k.cap) * sizeof(QNode4));  // QNode4s backwards, then 64 B
-    k.nodes = take(size_t(k.cap) * sizeof(BvhNode));       // directly behind them
-    k.sq = take(size_t(k.cap) * sizeof(QNode4));
-    k.range = take(size_t(k.cap) * sizeof(uint2));
-    k.qlist = take(size_t(k.cap) * sizeof(uint2));
-    k.hgt = take(size_t(k.cap));
-    k.order = take(size_t(k.cap) * sizeof(uint32_t));
-    k.level = take(size_t(kRefitLevels) * sizeof(uint32_t));
-    k.qsrc = take(4 * size_t(k.cap) * sizeof(int32_t));
+    k.part = A.take<float>(size_t(kBuildParts) * 6);
+    k.prims = A.take<uint32_t>(nt);
+    A.take<char>(64 + size_t(k.cap) * sizeof(QNode4));  // QNode4s backwards, then 64 B
+    k.nodes = A.take<BvhNode>(k.cap);                   // directly behind them
+    k.sq = A.take<QNode4>(k.cap);
+    k.range = A.take<uint2>(k.cap);
+    k.qlist = A.take<uint2>(k.cap);
+    k.hgt = A.take<uint8_t>(k.cap);
+    k.order = A.take<uint32_t>(k.cap);
+    k.level = A.take<uint32_t>(size_t(kRefitLevels));
+    k.qsrc = A.take<int32_t>(4 * size_t(k.cap));
     max_tris = std::max(max_tris, nt);
     max_verts = std::max(max_verts, uint32_t(nverts[i]));
     max_cap = std::max(max_cap, k.cap);
   }
-  {
-    const int r = ensure(c, &c->d_build, &c->build_cap, total);
-    if (r) return r;
-  }
-  if (c->h_build_cap < head_bytes) {
-    if (c->h_build) HIPCHK(c, hipHostFree(c->h_build));
-    c->h_build = nullptr;
-    c->h_build_cap = 0;
-    const size_t want = std::max(head_bytes, size_t(1) << 16);
-    HIPCHK(c, hipHostMalloc(&c->h_build, want, hipHostMallocDefault));
-    c->h_build_cap = want;
-  }
-  char* d = static_cast<char*>(c->d_build);
-  char* h = static_cast<char*>(c->h_build);
-  BuildJob* bjobs = reinterpret_cast<BuildJob*>(h + o_bjobs);
-  RefitJob* rjobs = reinterpret_cast<RefitJob*>(h + o_rjobs);
-  uint32_t* offsets = reinterpret_cast<uint32_t*>(h + o_offsets);
-  uint32_t* h_status = reinterpret_cast<uint32_t*>(h + o_status);
-  const BuildRec* h_rec = reinterpret_cast<const BuildRec*>(h + o_rec);
+  if (const int r = arena_reserve(c, &A)) return r;
+  BuildJob* bjobs = A.host(t_bjobs);
+  RefitJob* rjobs = A.host(t_rjobs);
+  uint32_t* offsets = A.host(t_offsets);
+  uint32_t* h_status = A.host(t_status);
+  const BuildRec* h_rec = A.host(t_rec);
   uint32_t first = 0;
   for (int i = 0; i < n; ++i) {
     const Scratch& k = sk[size_t(i)];
     BuildJob B{};
-    B.verts = static_cast<const float*>(sv[size_t(i)].dev);
-    B.faces = static_cast<const uint32_t*>(sf[size_t(i)].dev);
-    B.keys = reinterpret_cast<uint64_t*>(d + o_keys) + first;
-    B.sorted = reinterpret_cast<uint64_t*>(d + o_sorted) + first;
-    B.part = reinterpret_cast<float*>(d + k.part);
-    B.prims = reinterpret_cast<uint32_t*>(d + k.prims);
-    B.nodes = reinterpret_cast<BvhNode*>(d + k.nodes);
-    B.range = reinterpret_cast<uint2*>(d + k.range);
-    B.hgt = reinterpret_cast<uint8_t*>(d + k.hgt);
-    B.qlist = reinterpret_cast<uint2*>(d + k.qlist);
-    B.order = reinterpret_cast<uint32_t*>(d + k.order);
-    B.level = reinterpret_cast<uint32_t*>(d + k.level);
-    B.qsrc = reinterpret_cast<int32_t*>(d + k.qsrc);
-    B.rec = reinterpret_cast<BuildRec*>(d + o_rec) + i;
+    B.verts = stage.dev<float>(4 * size_t(i) + kVerts);
+    B.faces = stage.dev<uint32_t>(4 * size_t(i) + kFaces);
+    B.keys = A.dev(t_keys) + first;
+    B.sorted = A.dev(t_sorted) + first;
+    B.part = A.dev(k.part);
+    B.prims = A.dev(k.prims);
+    B.nodes = A.dev(k.nodes);
+    B.range = A.dev(k.range);
+    B.hgt = A.dev(k.hgt);
+    B.qlist = A.dev(k.qlist);
+    B.order = A.dev(k.order);
+    B.level = A.dev(k.level);
+    B.qsrc = A.dev(k.qsrc);
+    B.rec = A.dev(t_rec) + i;
     B.ntris = uint32_t(nfaces[i]);
     B.nverts = uint32_t(nverts[i]);
     B.cap = k.cap;
@@ -377,8 +352,8 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
     R.qsrc = B.qsrc;
     R.verts = B.verts;
     R.s_nodes = B.nodes;
-    R.s_q = reinterpret_cast<QNode4*>(d + k.sq);
-    R.s_grid = reinterpret_cast<QGrid*>(d + o_grid) + i;
+    R.s_q = A.dev(k.sq);
+    R.s_grid = A.dev(t_grid) + i;
     R.ntris = B.ntris;
     R.nverts = B.nverts;
     rjobs[i] = R;  // nnodes, nq, height: the topology and collapse launches'
@@ -390,18 +365,18 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
       HIPCHK(c, hipStreamWaitEvent(s, c->slots[size_t(slots[i])].ready, 0));
   }
   offsets[n] = first;
-  HIPCHK(c, hipMemcpyAsync(d, h, o_rec, hipMemcpyHostToDevice, s));
-  const BuildJob* d_bjobs = reinterpret_cast<const BuildJob*>(d + o_bjobs);
-  RefitJob* d_rjobs = reinterpret_cast<RefitJob*>(d + o_rjobs);
-  uint32_t* d_status = reinterpret_cast<uint32_t*>(d + o_status);
+  HIPCHK(c, arena_copy(A, 0, m_rec, true, s));
+  const BuildJob* d_bjobs = A.dev(t_bjobs);
+  RefitJob* d_rjobs = A.dev(t_rjobs);
+  uint32_t* d_status = A.dev(t_status);
 
   // ---- phase 1: the whole image into scratch ----
   HIPCHK(c, launch_build_check(s, d_bjobs, n, max_tris, d_status));
   HIPCHK(c, launch_build_keys(s, d_bjobs, n, max_tris, d_status));
   if (first) {
-    const uint64_t* d_keys = reinterpret_cast<const uint64_t*>(d + o_keys);
-    uint64_t* d_sorted = reinterpret_cast<uint64_t*>(d + o_sorted);
-    const uint32_t* d_offsets = reinterpret_cast<const uint32_t*>(d + o_offsets);
+    const uint64_t* d_keys = A.dev(t_keys);
+    uint64_t* d_sorted = A.dev(t_sorted);
+    const uint32_t* d_offsets = A.dev(t_offsets);
     size_t tmp_bytes = 0;
     HIPCHK(c, build_sort(s, nullptr, &tmp_bytes, d_keys, d_sorted, first, n, d_offsets));
     const int r = ensure(c, &c->d_sort, &c->sort_cap, std::max<size_t>(tmp_bytes, 256));
@@ -415,21 +390,21 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
   HIPCHK(c, launch_refit_grid(s, d_rjobs, n, d_status));
   HIPCHK(c, launch_build_collapse(s, d_bjobs, d_rjobs, n));
   HIPCHK(c, launch_refit_quant(s, d_rjobs, n, max_cap, d_status));
-  HIPCHK(c, hipMemcpyAsync(h + o_status, d + o_status, o_jobs2 - o_status, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, arena_copy(A, m_status, m_jobs2, false, s));
   HIPCHK(c, hipStreamSynchronize(s));  // the records: the call's read of its own results
   for (int i = 0; i < n; ++i) {
     const uint32_t st = h_status[i];
     if (st & build::kBadFace)
-      return fail(c, SPRAY_RT_ERR_ARG, "build (slot %d): face index out of range", slots[i]);
+      return fail_job(i, SPRAY_RT_ERR_ARG, "build (slot %d): face index out of range", slots[i]);
     if (st & refit::kBadVertex)
-      return fail(c, SPRAY_RT_ERR_ARG,
+      return fail_job(i, SPRAY_RT_ERR_ARG,
                   "build (slot %d): non-finite coordinate of a referenced vertex", slots[i]);
     if (st)
-      return fail(c, SPRAY_RT_ERR_LIMIT,
+      return fail_job(i, SPRAY_RT_ERR_LIMIT,
                   "build (slot %d): boxes beyond the range of the quantized node grid", slots[i]);
     if (h_rec[i].depth > kMaxDepth || h_rec[i].stack_bound > kQ4Stack ||
         h_rec[i].nnodes > sk[size_t(i)].cap || h_rec[i].nq > sk[size_t(i)].cap)
-      return fail(c, SPRAY_RT_ERR_LIMIT, "build (slot %d): tree deeper than kMaxDepth", slots[i]);
+      return fail_job(i, SPRAY_RT_ERR_LIMIT, "build (slot %d): tree deeper than kMaxDepth", slots[i]);
   }
 
   // ---- the exact images: every allocation before any slot changes ----
@@ -439,20 +414,20 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
   for (int i = 0; i < n; ++i) maxslot = std::max(maxslot, slots[i]);
   for (int i = 0; i < n; ++i) {
     layout_slot_image(&img[size_t(i)], h_rec[i].nnodes, nfaces[i], nverts[i], h_rec[i].nq,
-                      sc[size_t(i)].dev != nullptr, sn[size_t(i)].dev != nullptr, true);
+                      colors_of(i) != nullptr, normals_of(i) != nullptr, true);
     const size_t have = size_t(slots[i]) < c->slots.size() ? c->slots[size_t(slots[i])].bytes : 0;
     if (have >= img[size_t(i)].nbytes) continue;
     const hipError_t e = hipMalloc(&fresh[size_t(i)], img[size_t(i)].nbytes);
     if (e != hipSuccess) {
       for (void* p : fresh)
         if (p) (void)hipFree(p);
-      return fail(c, SPRAY_RT_ERR_HIP, "build (slot %d): hipMalloc of %zu bytes: %s", slots[i],
+      return fail_job(i, SPRAY_RT_ERR_HIP, "build (slot %d): hipMalloc of %zu bytes: %s", slots[i],
                   img[size_t(i)].nbytes, hipGetErrorString(e));
     }
   }
   if (size_t(maxslot) >= c->slots.size()) c->slots.resize(size_t(maxslot) + 1);
-  RefitJob* jobs2 = reinterpret_cast<RefitJob*>(h + o_jobs2);
-  CopyJob* copies = reinterpret_cast<CopyJob*>(h + o_copies);
+  RefitJob* jobs2 = A.host(t_jobs2);
+  CopyJob* copies = A.host(t_copies);
   int ncopies = 0;
   size_t max_words = 0;
   uint32_t max_nodes = 0;
@@ -479,7 +454,7 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
     R.nodes = const_cast<BvhNode*>(sh.desc.nodes);
     R.tris = const_cast<float*>(sh.desc.tris);
     R.normals = const_cast<float*>(sh.desc.normals);
-    R.vnormals = static_cast<const float*>(sn[size_t(i)].dev);
+    R.vnormals = normals_of(i);
     R.nnodes = rec.nnodes;
     R.nq = rec.nq;
     R.height = rec.height;
@@ -493,7 +468,7 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
     };
     copy(sh.desc.prims, B.prims, B.ntris);
     copy(sh.desc.faces, B.faces, 3 * size_t(B.ntris));
-    if (sh.desc.colors) copy(sh.desc.colors, sc[size_t(i)].dev, B.nverts);
+    if (sh.desc.colors) copy(sh.desc.colors, colors_of(i), B.nverts);
     copy(base + sh.refit.offset, B.order, rec.nnodes);
     copy(base + sh.refit.o_level(rec.nnodes), B.level, size_t(kRefitLevels));
     copy(base + sh.refit.o_qsrc(rec.nnodes), B.qsrc, 4 * size_t(rec.nq));
@@ -501,15 +476,25 @@ int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots, const floa
   c->slots_dirty = true;
 
   // ---- phase 2: commit ----
-  HIPCHK(c, hipMemcpyAsync(d + o_jobs2, h + o_jobs2, head_bytes - o_jobs2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, arena_copy(A, m_jobs2, A.head, true, s));
   HIPCHK(c, hipStreamSynchronize(s));  // the pinned tables are free for the next call
   if (ncopies)
-    HIPCHK(c, launch_build_copy(s, reinterpret_cast<const CopyJob*>(d + o_copies), ncopies,
-                                max_words));
-  HIPCHK(c, launch_refit_commit(s, reinterpret_cast<const RefitJob*>(d + o_jobs2), n, max_nodes,
-                                max_tris, max_verts, d_bounds));
-  if (stage_bytes) HIPCHK(c, hipStreamSynchronize(s));  // host arrays: done on return
+    HIPCHK(c, launch_build_copy(s, A.dev(t_copies), ncopies, max_words));
+  HIPCHK(c, launch_refit_commit(s, A.dev(t_jobs2), n, max_nodes, max_tris, max_verts, d_bounds));
+  if (stage.any) HIPCHK(c, hipStreamSynchronize(s));  // host arrays: done on return
   return SPRAY_RT_OK;
 }
 
-}  // extern "C"
+}  // namespace detail
+}  // namespace spray_rt
+
+extern "C" int spray_rt_domains_build(spray_rt_ctx_t c, int n, const int* slots,
+                                      const float* const* verts, const size_t* nverts,
+                                      const uint32_t* const* faces, const size_t* nfaces,
+                                      const uint32_t* const* colors_rgb,
+                                      const float* const* vnormals, float* d_bounds) {
+  if (!c) return SPRAY_RT_ERR_ARG;
+  int failed_job;
+  return domains_build(c, n, slots, verts, nverts, faces, nfaces, colors_rgb, vnormals, d_bounds,
+                       &failed_job);
+}

@@ -22,6 +22,7 @@
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
+#include "block_scan.h"
 #include "build_common.h"
 #include "build_kernels.h"
 
@@ -34,25 +35,6 @@ using namespace build;
 constexpr int kCodeBlock = 256;
 constexpr int kTreeBlock = 512;
 constexpr int32_t kEmptyChild = INT32_MIN;  // bvh_build.h kNoChild
-
-// Exclusive sum over the block's threads in thread order; *total = the sum.
-// Every thread of the block calls it.
-template <int B>
-__device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* s, uint32_t* total) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int off = 1; off < B; off <<= 1) {
-    const uint32_t x = t >= off ? s[t - off] : 0u;
-    __syncthreads();
-    s[t] += x;
-    __syncthreads();
-  }
-  *total = s[B - 1];
-  const uint32_t excl = s[t] - v;
-  __syncthreads();
-  return excl;
-}
 
 __global__ __launch_bounds__(kCodeBlock) void build_check_kernel(const BuildJob* __restrict__ jobs,
                                                                 uint32_t* __restrict__ status) {

@@ -23,6 +23,7 @@
 // ordering.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.h"
 #include "iso_common.h"
 #include "iso_kernels.h"
 
@@ -32,25 +33,6 @@ namespace {
 using namespace iso;
 
 constexpr int kScanBlock = 512;
-
-// Exclusive sum over the block's threads in thread order; *total = the sum.
-// Every thread of the block calls it.
-template <int B, typename T>
-__device__ inline T block_excl_scan(T v, T* s, T* total) {
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-  for (int off = 1; off < B; off <<= 1) {
-    const T x = t >= off ? s[t - off] : T(0);
-    __syncthreads();
-    s[t] += x;
-    __syncthreads();
-  }
-  *total = s[B - 1];
-  const T excl = s[t] - v;
-  __syncthreads();
-  return excl;
-}
 
 struct Point {
   int i, j, k;

@@ -150,7 +150,9 @@ int extract_host(const spray_rt_grid& g, bool emit, bool with_normals, HostMesh*
 // ---- the device extraction: count, the host read, emit ----
 
 struct IsoCall {
-  size_t o_jobs = 0, o_status = 0, o_rec = 0, o_outs = 0, head_bytes = 0;
+  HeadTake<IsoJob> jobs;  // in the context's iso arena
+  HeadTake<IsoOut> outs;
+  size_t m_outs = 0;  // the mark in front of outs
   uint32_t max_blocks = 0;
   bool staged = false;  // some field came from host memory
   std::vector<IsoRec> rec;
@@ -177,66 +179,46 @@ int iso_count(spray_rt_ctx* c, int n, const spray_rt_grid* grids, const int* slo
   hipStream_t s = stream_of(c);
 
   // ---- layout: tables (mirrored in pinned memory), then fields and scratch ----
-  call->o_jobs = 0;
-  call->o_status = call->o_jobs + align256(nj * sizeof(IsoJob));
-  call->o_rec = call->o_status + align256(nj * sizeof(uint32_t));
-  call->o_outs = call->o_rec + align256(nj * sizeof(IsoRec));
-  call->head_bytes = call->o_outs + align256(nj * sizeof(IsoOut));
-  size_t total = call->head_bytes;
-  auto take = [&](size_t bytes) {
-    const size_t o = total;
-    total += align256(bytes);
-    return o;
-  };
+  JobArena& A = c->iso;
+  A.reset();
+  call->jobs = A.take_head<IsoJob>(nj);
+  const size_t m_status = A.mark();
+  const auto t_status = A.take_head<uint32_t>(nj);
+  const size_t m_rec = A.mark();
+  const auto t_rec = A.take_head<IsoRec>(nj);
+  call->m_outs = A.mark();
+  call->outs = A.take_head<IsoOut>(nj);
   struct Scratch {
-    size_t values = SIZE_MAX, code, vblock, fblock;
+    Take<uint32_t> code, vblock, fblock;
     uint32_t npoints, nblocks;
   };
   std::vector<Scratch> sk(nj);
+  Stager stage;  // item i: grid i's field, a host one staged inside the arena
   for (int i = 0; i < n; ++i) {
     const spray_rt_grid& g = grids[i];
     Scratch& k = sk[size_t(i)];
     k.npoints = uint32_t(g.dims[0]) * uint32_t(g.dims[1]) * uint32_t(g.dims[2]);
     k.nblocks = (k.npoints + iso::kIsoBlock - 1) / iso::kIsoBlock;
-    if (!is_device_ptr(g.values)) {
-      k.values = take(size_t(k.npoints) * sizeof(float));
-      call->staged = true;
-    }
-    k.code = take(size_t(k.npoints) * sizeof(uint32_t));
-    k.vblock = take(size_t(k.nblocks) * sizeof(uint32_t));
-    k.fblock = take(size_t(k.nblocks) * sizeof(uint32_t));
+    stage.place(g.values, size_t(k.npoints) * sizeof(float), &A);
+    k.code = A.take<uint32_t>(k.npoints);
+    k.vblock = A.take<uint32_t>(k.nblocks);
+    k.fblock = A.take<uint32_t>(k.nblocks);
     call->max_blocks = std::max(call->max_blocks, k.nblocks);
   }
-  {
-    const int r = ensure(c, &c->d_iso, &c->iso_cap, total);
-    if (r) return r;
-  }
-  if (c->h_iso_cap < call->head_bytes) {
-    if (c->h_iso) HIPCHK(c, hipHostFree(c->h_iso));
-    c->h_iso = nullptr;
-    c->h_iso_cap = 0;
-    const size_t want = std::max(call->head_bytes, size_t(1) << 16);
-    HIPCHK(c, hipHostMalloc(&c->h_iso, want, hipHostMallocDefault));
-    c->h_iso_cap = want;
-  }
-  char* d = static_cast<char*>(c->d_iso);
-  char* h = static_cast<char*>(c->h_iso);
-  IsoJob* jobs = reinterpret_cast<IsoJob*>(h + call->o_jobs);
-  uint32_t* h_status = reinterpret_cast<uint32_t*>(h + call->o_status);
+  call->staged = stage.any;
+  if (const int r = arena_reserve(c, &A)) return r;
+  HIPCHK(c, stage.copy(A.d, s));
+  IsoJob* jobs = A.host(call->jobs);
+  uint32_t* h_status = A.host(t_status);
   for (int i = 0; i < n; ++i) {
     const spray_rt_grid& g = grids[i];
     const Scratch& k = sk[size_t(i)];
     IsoJob J{};
-    J.values = g.values;
-    if (k.values != SIZE_MAX) {
-      J.values = reinterpret_cast<const float*>(d + k.values);
-      HIPCHK(c, hipMemcpyAsync(d + k.values, g.values, size_t(k.npoints) * sizeof(float),
-                               hipMemcpyHostToDevice, s));
-    }
-    J.code = reinterpret_cast<uint32_t*>(d + k.code);
-    J.vblock = reinterpret_cast<uint32_t*>(d + k.vblock);
-    J.fblock = reinterpret_cast<uint32_t*>(d + k.fblock);
-    J.rec = reinterpret_cast<IsoRec*>(d + call->o_rec) + i;
+    J.values = stage.dev<float>(size_t(i));
+    J.code = A.dev(k.code);
+    J.vblock = A.dev(k.vblock);
+    J.fblock = A.dev(k.fblock);
+    J.rec = A.dev(t_rec) + i;
     J.nx = g.dims[0];
     J.ny = g.dims[1];
     J.nz = g.dims[2];
@@ -251,15 +233,13 @@ int iso_count(spray_rt_ctx* c, int n, const spray_rt_grid* grids, const int* slo
     jobs[i] = J;
     h_status[i] = 0;
   }
-  HIPCHK(c, hipMemcpyAsync(d, h, call->o_rec, hipMemcpyHostToDevice, s));
-  const IsoJob* d_jobs = reinterpret_cast<const IsoJob*>(d + call->o_jobs);
-  HIPCHK(c, launch_iso_count(s, d_jobs, n, call->max_blocks,
-                             reinterpret_cast<uint32_t*>(d + call->o_status)));
+  HIPCHK(c, arena_copy(A, 0, m_rec, true, s));
+  const IsoJob* d_jobs = A.dev(call->jobs);
+  HIPCHK(c, launch_iso_count(s, d_jobs, n, call->max_blocks, A.dev(t_status)));
   HIPCHK(c, launch_iso_scan(s, d_jobs, n));
-  HIPCHK(c, hipMemcpyAsync(h + call->o_status, d + call->o_status, call->o_outs - call->o_status,
-                           hipMemcpyDeviceToHost, s));
+  HIPCHK(c, arena_copy(A, m_status, call->m_outs, false, s));
   HIPCHK(c, hipStreamSynchronize(s));  // the sizes: the extraction's host read
-  const IsoRec* h_rec = reinterpret_cast<const IsoRec*>(h + call->o_rec);
+  const IsoRec* h_rec = A.host(t_rec);
   call->rec.assign(h_rec, h_rec + n);
   for (int i = 0; i < n; ++i) {
     if (h_status[i] & iso::kBadSample)
@@ -273,14 +253,11 @@ int iso_count(spray_rt_ctx* c, int n, const spray_rt_grid* grids, const int* slo
 // The emit pass of a counted call into outs[n].
 int iso_emit(spray_rt_ctx* c, int n, const IsoCall& call, const std::vector<IsoOut>& outs) {
   hipStream_t s = stream_of(c);
-  char* d = static_cast<char*>(c->d_iso);
-  char* h = static_cast<char*>(c->h_iso);
-  std::memcpy(h + call.o_outs, outs.data(), size_t(n) * sizeof(IsoOut));
-  HIPCHK(c, hipMemcpyAsync(d + call.o_outs, h + call.o_outs, size_t(n) * sizeof(IsoOut),
-                           hipMemcpyHostToDevice, s));
+  const JobArena& A = c->iso;
+  std::memcpy(A.host(call.outs), outs.data(), size_t(n) * sizeof(IsoOut));
+  HIPCHK(c, arena_copy(A, call.m_outs, call.m_outs + size_t(n) * sizeof(IsoOut), true, s));
   HIPCHK(c, hipStreamSynchronize(s));  // the pinned tables are free for the next call
-  HIPCHK(c, launch_iso_emit(s, reinterpret_cast<const IsoJob*>(d + call.o_jobs),
-                            reinterpret_cast<const IsoOut*>(d + call.o_outs), n, call.max_blocks));
+  HIPCHK(c, launch_iso_emit(s, A.dev(call.jobs), A.dev(call.outs), n, call.max_blocks));
   return SPRAY_RT_OK;
 }
 
@@ -361,55 +338,41 @@ int spray_rt_domains_isosurface(spray_rt_ctx_t c, int n, const int* slots,
   if (r) return r;
 
   // ---- the meshes: context scratch, sized by the counts ----
-  std::vector<size_t> o_verts(nj), o_normals(nj), o_colors(nj), o_faces(nj), nv(nj), nf(nj);
-  size_t total = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = total;
-    total += align256(bytes);
-    return o;
-  };
-  for (int i = 0; i < n; ++i) {
-    const size_t k = size_t(i);
-    nv[k] = size_t(call.rec[k].nverts);
-    nf[k] = size_t(call.rec[k].nfaces);
-    o_verts[k] = take(3 * nv[k] * sizeof(float));
-    o_normals[k] = with_normals ? take(3 * nv[k] * sizeof(float)) : SIZE_MAX;
-    o_colors[k] = grids[i].has_color ? take(nv[k] * sizeof(uint32_t)) : SIZE_MAX;
-    o_faces[k] = take(3 * nf[k] * sizeof(uint32_t));
-  }
-  r = ensure(c, &c->d_isomesh, &c->isomesh_cap, std::max<size_t>(total, 256));
-  if (r) return r;
-  char* m = static_cast<char*>(c->d_isomesh);
+  Layout M;  // of d_isomesh
   std::vector<IsoOut> outs(nj, IsoOut{});
+  std::vector<Take<float>> t_verts(nj), t_normals(nj);
+  std::vector<Take<uint32_t>> t_colors(nj), t_faces(nj);
+  std::vector<size_t> nv(nj), nf(nj);
+  for (size_t k = 0; k < nj; ++k) {
+    outs[k].cap_verts = nv[k] = size_t(call.rec[k].nverts);
+    outs[k].cap_faces = nf[k] = size_t(call.rec[k].nfaces);
+    t_verts[k] = M.take<float>(3 * nv[k]);
+    if (with_normals) t_normals[k] = M.take<float>(3 * nv[k]);
+    if (grids[k].has_color) t_colors[k] = M.take<uint32_t>(nv[k]);
+    t_faces[k] = M.take<uint32_t>(3 * nf[k]);
+  }
+  r = ensure(c, &c->d_isomesh, &c->isomesh_cap, std::max<size_t>(M.used, 256));
+  if (r) return r;
   std::vector<const float*> pv(nj), pn(nj);
   std::vector<const uint32_t*> pc(nj), pf(nj);
   for (size_t k = 0; k < nj; ++k) {
     IsoOut& O = outs[k];
-    O.verts = reinterpret_cast<float*>(m + o_verts[k]);
-    O.normals = o_normals[k] == SIZE_MAX ? nullptr : reinterpret_cast<float*>(m + o_normals[k]);
-    O.colors = o_colors[k] == SIZE_MAX ? nullptr : reinterpret_cast<uint32_t*>(m + o_colors[k]);
-    O.faces = reinterpret_cast<uint32_t*>(m + o_faces[k]);
-    O.cap_verts = nv[k];
-    O.cap_faces = nf[k];
-    pv[k] = O.verts;
-    pn[k] = O.normals;
-    pc[k] = O.colors;
-    pf[k] = O.faces;
+    pv[k] = O.verts = t_verts[k].at(c->d_isomesh);
+    pn[k] = O.normals = t_normals[k] ? t_normals[k].at(c->d_isomesh) : nullptr;
+    pc[k] = O.colors = t_colors[k] ? t_colors[k].at(c->d_isomesh) : nullptr;
+    pf[k] = O.faces = t_faces[k].at(c->d_isomesh);
   }
   r = iso_emit(c, n, call, outs);
   if (r) return r;
 
   // ---- the slots: the device build on the extracted arrays ----
-  r = spray_rt_domains_build(c, n, slots, pv.data(), nv.data(), pf.data(), nf.data(), pc.data(),
-                             pn.data(), d_bounds);
-  if (r) {  // the build names the slot; name the grid as well
+  int job = -1;  // the build names the slot; name the grid as well
+  r = domains_build(c, n, slots, pv.data(), nv.data(), pf.data(), nf.data(), pc.data(), pn.data(),
+                    d_bounds, &job);
+  if (r) {
     const std::string msg = c->err;
-    int slot = -1, grid = -1;
-    const size_t at = msg.find("slot ");
-    if (at != std::string::npos && sscanf(msg.c_str() + at, "slot %d", &slot) == 1)
-      for (int i = 0; i < n; ++i)
-        if (slots[i] == slot) grid = i;
-    if (grid >= 0) return fail(c, r, "isosurface (grid %d, slot %d): %s", grid, slot, msg.c_str());
+    if (job >= 0)
+      return fail(c, r, "isosurface (grid %d, slot %d): %s", job, slots[job], msg.c_str());
     return fail(c, r, "isosurface: %s", msg.c_str());
   }
   if (nfaces_out)

@@ -128,8 +128,6 @@ int check_slot(spray_rt_ctx* c, int slot) {
   return SPRAY_RT_OK;
 }
 
-size_t align_up(size_t x) { return align256(x); }
-
 }  // namespace
 
 extern "C" {
@@ -185,62 +183,37 @@ int spray_rt_domains_refit(spray_rt_ctx_t c, int n, const int* slots, const floa
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = stream_of(c);
 
-  // ---- layout: host-pointer staging, job table, status, grids, scratch image ----
-  std::vector<const float*> dv(size_t(n), nullptr), dn(size_t(n), nullptr);
-  std::vector<size_t> stage_v(size_t(n), SIZE_MAX), stage_n(size_t(n), SIZE_MAX);
-  size_t stage_bytes = 0;
+  // ---- caller arrays: device pointers as they are, host arrays staged ----
+  Stager stage;  // items 2 i, 2 i + 1: job i's vertices and normals
   for (int i = 0; i < n; ++i) {
     const SlotHost& sh = c->slots[size_t(slots[i])];
     const size_t vb = 3 * size_t(sh.desc.nverts) * sizeof(float);
-    if (!vb) continue;
-    if (is_device_ptr(verts[i])) {
-      dv[size_t(i)] = verts[i];
-    } else {
-      stage_v[size_t(i)] = stage_bytes;
-      stage_bytes += align_up(vb);
-    }
-    if (!sh.desc.normals) continue;
-    if (is_device_ptr(vnormals[i])) {
-      dn[size_t(i)] = vnormals[i];
-    } else {
-      stage_n[size_t(i)] = stage_bytes;
-      stage_bytes += align_up(vb);
-    }
+    stage.place(vb ? verts[i] : nullptr, vb);
+    stage.place(vb && sh.desc.normals ? vnormals[i] : nullptr, vb);
   }
-  if (stage_bytes) {
-    int r = ensure(c, &c->d_stage, &c->stage_cap, stage_bytes);
-    if (r) return r;
-  }
-  const size_t o_status = align_up(size_t(n) * sizeof(RefitJob));
-  const size_t o_grid = o_status + align_up(size_t(n) * sizeof(uint32_t));
-  size_t total = o_grid + align_up(size_t(n) * sizeof(QGrid));
-  const size_t head_bytes = o_grid;  // job table + status words: the pinned mirror
+  if (stage.any)
+    if (const int r = ensure(c, &c->d_stage, &c->stage_cap, stage.own.used)) return r;
+
+  // ---- layout: job table, status (mirrored in pinned memory), grids, scratch image ----
   const size_t nj = size_t(n);
-  std::vector<size_t> o_nodes(nj, 0), o_q(nj, 0);
+  JobArena& A = c->refit;
+  A.reset();
+  const auto t_jobs = A.take_head<RefitJob>(nj);
+  const size_t m_status = A.mark();
+  const auto t_status = A.take_head<uint32_t>(nj);
+  const auto t_grid = A.take<QGrid>(nj);
+  std::vector<Take<BvhNode>> t_nodes(nj);
+  std::vector<Take<QNode4>> t_q(nj);
   for (int i = 0; i < n; ++i) {
     const SlotHost& sh = c->slots[size_t(slots[i])];
-    o_nodes[size_t(i)] = total;
-    total += align_up(size_t(sh.desc.nnodes) * sizeof(BvhNode));
-    o_q[size_t(i)] = total;
-    total += align_up(size_t(sh.refit.nq) * sizeof(QNode4));
+    t_nodes[size_t(i)] = A.take<BvhNode>(sh.desc.nnodes);
+    t_q[size_t(i)] = A.take<QNode4>(sh.refit.nq);
   }
-  {
-    int r = ensure(c, &c->d_refit, &c->refit_cap, total);
-    if (r) return r;
-  }
-  if (c->h_refit_cap < head_bytes) {
-    if (c->h_refit) HIPCHK(c, hipHostFree(c->h_refit));
-    c->h_refit = nullptr;
-    c->h_refit_cap = 0;
-    const size_t want = std::max(head_bytes, size_t(1) << 16);
-    HIPCHK(c, hipHostMalloc(&c->h_refit, want, hipHostMallocDefault));
-    c->h_refit_cap = want;
-  }
-  char* d = static_cast<char*>(c->d_refit);
-  char* h = static_cast<char*>(c->h_refit);
-  RefitJob* jobs = reinterpret_cast<RefitJob*>(h);
-  uint32_t* h_status = reinterpret_cast<uint32_t*>(h + o_status);
-  uint32_t* d_status = reinterpret_cast<uint32_t*>(d + o_status);
+  if (const int r = arena_reserve(c, &A)) return r;
+  HIPCHK(c, stage.copy(c->d_stage, s));
+  RefitJob* jobs = A.host(t_jobs);
+  uint32_t* h_status = A.host(t_status);
+  uint32_t* d_status = A.dev(t_status);
   uint32_t max_tris = 0, max_nodes = 0, max_verts = 0, max_nq = 0;
   uint32_t level_max[kRefitLevels] = {};
   int height = 0;
@@ -250,18 +223,6 @@ int spray_rt_domains_refit(spray_rt_ctx_t c, int n, const int* slots, const floa
     if (sh.ready) HIPCHK(c, hipStreamWaitEvent(s, sh.ready, 0));
     char* base = static_cast<char*>(sh.dmem);
     const size_t nn = sh.desc.nnodes;
-    if (stage_v[size_t(i)] != SIZE_MAX) {
-      char* dst = static_cast<char*>(c->d_stage) + stage_v[size_t(i)];
-      HIPCHK(c, hipMemcpyAsync(dst, verts[i], 3 * size_t(sh.desc.nverts) * sizeof(float),
-                               hipMemcpyHostToDevice, s));
-      dv[size_t(i)] = reinterpret_cast<const float*>(dst);
-    }
-    if (stage_n[size_t(i)] != SIZE_MAX) {
-      char* dst = static_cast<char*>(c->d_stage) + stage_n[size_t(i)];
-      HIPCHK(c, hipMemcpyAsync(dst, vnormals[i], 3 * size_t(sh.desc.nverts) * sizeof(float),
-                               hipMemcpyHostToDevice, s));
-      dn[size_t(i)] = reinterpret_cast<const float*>(dst);
-    }
     RefitJob J{};
     J.nodes = const_cast<BvhNode*>(sh.desc.nodes);
     J.tris = const_cast<float*>(sh.desc.tris);
@@ -271,11 +232,11 @@ int spray_rt_domains_refit(spray_rt_ctx_t c, int n, const int* slots, const floa
     J.order = reinterpret_cast<const uint32_t*>(base + sh.refit.offset);
     J.level = reinterpret_cast<const uint32_t*>(base + sh.refit.o_level(nn));
     J.qsrc = reinterpret_cast<const int32_t*>(base + sh.refit.o_qsrc(nn));
-    J.verts = dv[size_t(i)];
-    J.vnormals = dn[size_t(i)];
-    J.s_nodes = reinterpret_cast<BvhNode*>(d + o_nodes[size_t(i)]);
-    J.s_q = reinterpret_cast<QNode4*>(d + o_q[size_t(i)]);
-    J.s_grid = reinterpret_cast<QGrid*>(d + o_grid) + i;
+    J.verts = stage.dev<float>(2 * size_t(i));
+    J.vnormals = stage.dev<float>(2 * size_t(i) + 1);
+    J.s_nodes = A.dev(t_nodes[size_t(i)]);
+    J.s_q = A.dev(t_q[size_t(i)]);
+    J.s_grid = A.dev(t_grid) + i;
     J.nnodes = sh.desc.nnodes;
     J.ntris = sh.desc.ntris;
     J.nverts = sh.desc.nverts;
@@ -291,8 +252,8 @@ int spray_rt_domains_refit(spray_rt_ctx_t c, int n, const int* slots, const floa
     for (int lv = 1; lv <= sh.refit.height; ++lv)
       level_max[lv] = std::max(level_max[lv], sh.refit.level[lv + 1] - sh.refit.level[lv]);
   }
-  HIPCHK(c, hipMemcpyAsync(d, h, head_bytes, hipMemcpyHostToDevice, s));
-  const RefitJob* d_jobs = reinterpret_cast<const RefitJob*>(d);
+  HIPCHK(c, arena_copy(A, 0, A.head, true, s));
+  const RefitJob* d_jobs = A.dev(t_jobs);
 
   // ---- phase 1: fit and quantize into scratch, flag what cannot be done ----
   HIPCHK(c, launch_refit_check_tris(s, d_jobs, n, max_tris, d_status));
@@ -300,8 +261,7 @@ int spray_rt_domains_refit(spray_rt_ctx_t c, int n, const int* slots, const floa
     HIPCHK(c, launch_refit_fit_level(s, d_jobs, n, lv, level_max[lv]));
   HIPCHK(c, launch_refit_grid(s, d_jobs, n, d_status));
   HIPCHK(c, launch_refit_quant(s, d_jobs, n, max_nq, d_status));
-  HIPCHK(c, hipMemcpyAsync(h_status, d_status, size_t(n) * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, s));
+  HIPCHK(c, arena_copy(A, m_status, m_status + nj * sizeof(uint32_t), false, s));
   HIPCHK(c, hipStreamSynchronize(s));  // the call's one host read
   for (int i = 0; i < n; ++i) {
     if (!h_status[i]) continue;
@@ -314,7 +274,7 @@ int spray_rt_domains_refit(spray_rt_ctx_t c, int n, const int* slots, const floa
 
   // ---- phase 2: commit ----
   HIPCHK(c, launch_refit_commit(s, d_jobs, n, max_nodes, max_tris, max_verts, d_bounds));
-  if (stage_bytes) HIPCHK(c, hipStreamSynchronize(s));  // host arrays: done on return
+  if (stage.any) HIPCHK(c, hipStreamSynchronize(s));  // host arrays: done on return
   return SPRAY_RT_OK;
 }
 

@@ -71,6 +71,24 @@ int ensure(spray_rt_ctx* c, void** buf, size_t* cap, size_t bytes) {
   return SPRAY_RT_OK;
 }
 
+int arena_reserve(spray_rt_ctx* c, JobArena* a) {
+  const int r = ensure(c, &a->d, &a->d_cap, a->used);
+  if (r) return r;
+  if (a->h_cap >= a->head) return SPRAY_RT_OK;
+  if (a->h) HIPCHK(c, hipHostFree(a->h));
+  a->h = nullptr;
+  a->h_cap = 0;
+  const size_t want = std::max(a->head, size_t(1) << 16);
+  HIPCHK(c, hipHostMalloc(&a->h, want, hipHostMallocDefault));
+  a->h_cap = want;
+  return SPRAY_RT_OK;
+}
+
+void arena_release(JobArena* a) {
+  if (a->d) (void)hipFree(a->d);
+  if (a->h) (void)hipHostFree(a->h);
+}
+
 void layout_slot_image(SlotImage* out, size_t nnodes, size_t nfaces, size_t nverts, size_t nq,
                        bool colors, bool normals, bool quantized) {
   // QGrid at nodes - 32, QNode4 i at nodes - 64 - 64 (i + 1) (rt_common.h)
@@ -391,12 +409,10 @@ int spray_rt_destroy(spray_rt_ctx_t c) {
   void* bufs[] = {c->d_slots, c->d_boxes, c->d_dom2slot, c->d_domtrav, c->d_owner, c->d_tlas, c->d_seg_slot,
                   c->d_seg_off, c->d_stage, c->d_stage2, c->d_stage3,
                   c->d_block_counts, c->d_heads, c->d_sel, c->d_bsdf, c->d_frame, c->d_fstats, c->d_ftab,
-                  c->d_refit, c->d_sah, c->d_build, c->d_sort, c->d_iso, c->d_isomesh};
+                  c->d_sah, c->d_sort, c->d_isomesh};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
-  if (c->h_iso) (void)hipHostFree(c->h_iso);
-  if (c->h_refit) (void)hipHostFree(c->h_refit);
-  if (c->h_build) (void)hipHostFree(c->h_build);
+  for (JobArena* a : {&c->refit, &c->build, &c->iso}) arena_release(a);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
   delete c;

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "job_arena.h"
 #include "rt_common.h"
 #include "rt_kernels.h"
 #include "spray_rt.h"
@@ -41,8 +42,6 @@ struct SlotHost {
   void* pinned = nullptr;      // staging for async uploads
   size_t pinned_bytes = 0;
 };
-
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 }  // namespace detail
 }  // namespace spray_rt
@@ -87,21 +86,13 @@ struct spray_rt_ctx {
   size_t stage2_cap = 0;
   void* d_stage3 = nullptr;
   size_t stage3_cap = 0;
-  void* d_refit = nullptr;  // refit job table, status words and scratch image
-  size_t refit_cap = 0;
-  void* h_refit = nullptr;  // pinned mirror of the job table and the status words
-  size_t h_refit_cap = 0;
+  // scratch of the batched slot calls (job_arena.h), one arena per call kind
+  spray_rt::detail::JobArena refit;  // job table, status words | grids, scratch image
+  spray_rt::detail::JobArena build;  // job tables, records | grids, keys, scratch images
+  spray_rt::detail::JobArena iso;    // job tables, records | staged fields, per-point scratch
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
-  void* d_build = nullptr;  // device build: job tables, records and the scratch images
-  size_t build_cap = 0;
-  void* h_build = nullptr;  // pinned mirror of the job tables and the records
-  size_t h_build_cap = 0;
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;
-  void* d_iso = nullptr;  // isosurface: job tables, records, staged fields, per-point scratch
-  size_t iso_cap = 0;
-  void* h_iso = nullptr;  // pinned mirror of the job tables and the records
-  size_t h_iso_cap = 0;
   void* d_isomesh = nullptr;  // isosurface into slots: the extracted meshes
   size_t isomesh_cap = 0;
   uint32_t* d_block_counts = nullptr;
@@ -188,6 +179,60 @@ hipStream_t stream_of(spray_rt_ctx* c);
 bool is_device_ptr(const void* p);
 // grows *buf to at least bytes (device memory)
 int ensure(spray_rt_ctx* c, void** buf, size_t* cap, size_t bytes);
+// Storage of a laid-out arena: the device side through ensure, the pinned
+// mirror of the head grow-only from 64 KiB.  A failed growth leaves the side
+// it was growing empty.
+int arena_reserve(spray_rt_ctx* c, JobArena* a);
+void arena_release(JobArena* a);
+// Async copy of the mirrored bytes [from, to) between marks: up = host to device.
+inline hipError_t arena_copy(const JobArena& a, size_t from, size_t to, bool up, hipStream_t s) {
+  assert(from <= to && to <= a.head);
+  char *d = static_cast<char*>(a.d) + from, *h = static_cast<char*>(a.h) + from;
+  return up ? hipMemcpyAsync(d, h, to - from, hipMemcpyHostToDevice, s)
+            : hipMemcpyAsync(h, d, to - from, hipMemcpyDeviceToHost, s);
+}
+
+// Caller arrays of a batched call, in host or in device memory: place() each
+// before anything is enqueued, make room, copy() once.  A call that staged
+// anything synchronizes before it returns.
+struct Stager {
+  struct Item {
+    const void* p;      // where the kernels read it (a host array: after copy())
+    size_t bytes, off;  // off == SIZE_MAX: used where it is
+  };
+  std::vector<Item> items;  // every placed array, null and empty ones too
+  Layout own;               // room for host arrays placed without a layout
+  bool any = false;         // some array is staged
+  // A host array gets a take of `in` (nullptr: own).
+  void place(const void* p, size_t bytes, Layout* in = nullptr) {
+    Item it{bytes ? p : nullptr, bytes, SIZE_MAX};  // an empty array reads as a null one
+    if (it.p && !is_device_ptr(p)) {
+      it.off = (in ? in : &own)->take<char>(bytes).off;
+      any = true;
+    }
+    items.push_back(it);
+  }
+  // One async copy per host array to base + its offset.
+  hipError_t copy(void* base, hipStream_t s) {
+    for (Item& it : items) {
+      if (it.off == SIZE_MAX) continue;
+      char* dst = static_cast<char*>(base) + it.off;
+      const hipError_t e = hipMemcpyAsync(dst, it.p, it.bytes, hipMemcpyHostToDevice, s);
+      if (e != hipSuccess) return e;
+      it.p = dst;
+    }
+    return hipSuccess;
+  }
+  template <class T>
+  const T* dev(size_t k) const { return static_cast<const T*>(items[k].p); }
+};
+
+// spray_rt_domains_build; *failed_job = the index of the job a failure names,
+// -1 where it names none.
+int domains_build(spray_rt_ctx* c, int n, const int* slots, const float* const* verts,
+                  const size_t* nverts, const uint32_t* const* faces, const size_t* nfaces,
+                  const uint32_t* const* colors_rgb, const float* const* vnormals,
+                  float* d_bounds, int* failed_job);
 // scene-path entry checks + lazy rebuild of the device scene tables
 int scene_common(spray_rt_ctx* c, const void* rays, size_t M, const void* out);
 // the kernels' view of the resident scene (coherence = the context's)

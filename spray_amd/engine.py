@@ -334,6 +334,15 @@ class RtContext:
     SLOT_NODES, SLOT_TRIS, SLOT_PRIMS, SLOT_QNODES4, SLOT_QGRID, SLOT_NORMALS = range(6)
     _SLOT_DTYPES = (np.uint8, np.float32, np.uint32, np.uint8, np.float32, np.float32)
 
+    def _bounds_out(self, bounds, n):
+        """Where a batched slot call writes its [n, 6] boxes: a new GPU tensor
+        (bounds True), the caller's tensor, or nowhere."""
+        if bounds is True:
+            import torch
+            return torch.empty((max(n, 1), 6), dtype=torch.float32,
+                               device="cuda:%d" % self._device)
+        return None if bounds is False else bounds
+
     def refit_domains(self, slots, verts, normals=None, bounds=False):
         """spray_rt_domains_refit: new vertex positions (and normals, for
         slots uploaded with them) for resident slots of unchanged topology.
@@ -371,13 +380,7 @@ class RtContext:
             npp = (C.c_void_p * max(n, 1))(*[pointer(x, s, "normals")
                                              for x, s in zip(normals, slots)])
         sl = (C.c_int * max(n, 1))(*slots)
-        out = None
-        if bounds is True:
-            import torch
-            out = torch.empty((max(n, 1), 6), dtype=torch.float32,
-                              device="cuda:%d" % self._device)
-        elif bounds is not False and bounds is not None:
-            out = bounds
+        out = self._bounds_out(bounds, n)
         b, k = _addr(out)
         self._check(lib().spray_rt_domains_refit(self.h, n, sl, vp, npp, b), "domains_refit")
         if bounds is True:
@@ -436,12 +439,7 @@ class RtContext:
                                                                for x in normals])
         sl = (C.c_int * m)(*slots)
         nvp, nfp = (C.c_size_t * m)(*nv), (C.c_size_t * m)(*nf)
-        out = None
-        if bounds is True:
-            import torch
-            out = torch.empty((m, 6), dtype=torch.float32, device="cuda:%d" % self._device)
-        elif bounds is not False and bounds is not None:
-            out = bounds
+        out = self._bounds_out(bounds, n)
         b, k = _addr(out)
         self._check(lib().spray_rt_domains_build(self.h, n, sl, vp, nvp, fp, nfp, cp, npp, b),
                     "domains_build")
@@ -504,12 +502,7 @@ class RtContext:
         arr, keep = _grid_table(grids)
         m = max(n, 1)
         sl = (C.c_int * m)(*slots)
-        out = None
-        if bounds is True:
-            import torch
-            out = torch.empty((m, 6), dtype=torch.float32, device="cuda:%d" % self._device)
-        elif bounds is not False and bounds is not None:
-            out = bounds
+        out = self._bounds_out(bounds, n)
         b, k = _addr(out)
         nf = (C.c_size_t * m)()
         self._check(lib().spray_rt_domains_isosurface(self.h, n, sl, arr, 1 if normals else 0, b,
