@@ -92,7 +92,13 @@ typedef struct spray_rt_ray_intersection {
   float Ns[3];
 } spray_rt_ray_intersection;
 
-/* Compact ray of the fused scene path: 32 B, two 16-B loads per lane. */
+/* Compact ray of the fused scene path: 32 B, two 16-B loads per lane.
+ * Every scene launch honours the record's own extents: a hit satisfies
+ * tnear < t <= tfar (t == tfar is accepted), in every domain the ray visits.
+ * The ray's domain list ignores them (intersectAabb with 0.001 and +inf).
+ * A record holding a NaN or an infinity in org or dir, an all-zero dir, a NaN
+ * tnear or a NaN tfar is a miss and not occluded; its neighbours are
+ * unaffected. */
 typedef struct spray_rt_ray {
   float org[3];
   float tnear;

@@ -1016,8 +1016,16 @@ void or_epilogue(const uint32_t* faces, const uint32_t* colors,
   }
 }
 
-void or_scene_intersect(const or_scene* s, const float* org, const float* dir,
-                        size_t n, or_hit* hits, or_counts* cnt, int nthreads) {
+/* Per-ray extents (tnear[n] / tfar[n], NULL = 0.001 / +inf) act on the
+ * triangle tests only: the domain list is intersectAabb with the reference's
+ * fixed 0.001 / +inf whatever the record says.  Every domain visit uses the
+ * ray's tnear; the closest hit starts from (tfar, ~0u), so t == tfar is
+ * accepted, and any hit accepts tnear < t <= tfar.  A NaN in either extent
+ * fails every comparison: the ray misses. */
+void or_scene_intersect_ext(const or_scene* s, const float* org,
+                            const float* dir, const float* tnear,
+                            const float* tfar, size_t n, or_hit* hits,
+                            or_counts* cnt, int nthreads) {
   uint64_t tn = 0, tt = 0, tv = 0;
 #ifdef _OPENMP
   int nt = nthreads > 0 ? nthreads : omp_get_max_threads();
@@ -1032,7 +1040,8 @@ void or_scene_intersect(const or_scene* s, const float* org, const float* dir,
                         ts, &over);
     ray_pre r;
     ray_prep(&r, org + 3 * i, dir + 3 * i);
-    float bt = OR_INF, bu = 0, bv = 0;
+    const float tnr = tnear ? tnear[i] : OR_RAY_EPSILON;
+    float bt = tfar ? tfar[i] : OR_INF, bu = 0, bv = 0;
     int bd = -1;
     uint32_t bpl = 0, bpo = 0xFFFFFFFFu;
     uint64_t a = 0, b = 0;
@@ -1044,7 +1053,7 @@ void or_scene_intersect(const or_scene* s, const float* org, const float* dir,
        * strict. */
       float lt = bt, lu = 0, lv = 0;
       uint32_t lp = bd >= 0 ? 0u : 0xFFFFFFFFu, ll = 0;
-      traverse(d->nodes, d->bvh->tri, d->bvh->order, &r, OR_RAY_EPSILON, &lt,
+      traverse(d->nodes, d->bvh->tri, d->bvh->order, &r, tnr, &lt,
                &lp, &ll, &lu, &lv, 0, 0.0f, &a, &b);
       ++tv;
       if (lt < bt || (bd < 0 && lp != 0xFFFFFFFFu)) {
@@ -1075,8 +1084,15 @@ void or_scene_intersect(const or_scene* s, const float* org, const float* dir,
   }
 }
 
-void or_scene_occluded(const or_scene* s, const float* org, const float* dir,
-                       size_t n, uint8_t* occ, or_counts* cnt, int nthreads) {
+void or_scene_intersect(const or_scene* s, const float* org, const float* dir,
+                        size_t n, or_hit* hits, or_counts* cnt, int nthreads) {
+  or_scene_intersect_ext(s, org, dir, NULL, NULL, n, hits, cnt, nthreads);
+}
+
+void or_scene_occluded_ext(const or_scene* s, const float* org,
+                           const float* dir, const float* tnear,
+                           const float* tfar, size_t n, uint8_t* occ,
+                           or_counts* cnt, int nthreads) {
   uint64_t tn = 0, tt = 0, tv = 0;
 #ifdef _OPENMP
   int nt = nthreads > 0 ? nthreads : omp_get_max_threads();
@@ -1099,8 +1115,8 @@ void or_scene_occluded(const or_scene* s, const float* org, const float* dir,
       float bt = 0, bu, bv;
       uint32_t bp = 0, bl = 0;
       o = (uint8_t)traverse(d->nodes, d->bvh->tri, d->bvh->order, &r,
-                            OR_RAY_EPSILON, &bt, &bp, &bl, &bu, &bv, 1, OR_INF,
-                            &a, &b);
+                            tnear ? tnear[i] : OR_RAY_EPSILON, &bt, &bp, &bl,
+                            &bu, &bv, 1, tfar ? tfar[i] : OR_INF, &a, &b);
       ++tv;
     }
     tn += a;
@@ -1110,6 +1126,11 @@ void or_scene_occluded(const or_scene* s, const float* org, const float* dir,
   if (cnt) {
     cnt->nodes = tn; cnt->tris = tt; cnt->visits = tv; cnt->rays = n;
   }
+}
+
+void or_scene_occluded(const or_scene* s, const float* org, const float* dir,
+                       size_t n, uint8_t* occ, or_counts* cnt, int nthreads) {
+  or_scene_occluded_ext(s, org, dir, NULL, NULL, n, occ, cnt, nthreads);
 }
 
 /* ------------------------------------------------------------------ */

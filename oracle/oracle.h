@@ -140,6 +140,18 @@ void or_scene_intersect(const or_scene*, const float* org, const float* dir,
                         size_t n, or_hit* hits, or_counts* cnt, int nthreads);
 void or_scene_occluded(const or_scene*, const float* org, const float* dir,
                        size_t n, uint8_t* occ, or_counts* cnt, int nthreads);
+/* The same with per-ray extents, tnear[n] / tfar[n] (NULL = 0.001 / +inf; the
+ * two calls above forward here with NULL).  The domain list ignores them
+ * (intersectAabb with 0.001 / +inf); every domain visit uses the ray's tnear;
+ * the closest hit starts from (tfar, 0xFFFFFFFF), so t == tfar is accepted,
+ * and a later list entry must be strictly nearer; any hit accepts
+ * tnear < t <= tfar.  A miss is written as by or_scene_intersect. */
+void or_scene_intersect_ext(const or_scene*, const float* org, const float* dir,
+                            const float* tnear, const float* tfar, size_t n,
+                            or_hit* hits, or_counts* cnt, int nthreads);
+void or_scene_occluded_ext(const or_scene*, const float* org, const float* dir,
+                           const float* tnear, const float* tfar, size_t n,
+                           uint8_t* occ, or_counts* cnt, int nthreads);
 /* PT point-light shadow spawn (ooc_shader_pt.h:93-171).  Writes rays for
  * primaries that hit and pass hasPositive(Lr); returns the count.
  * src_index_out[k] = primary index of shadow ray k (ascending). */

@@ -107,6 +107,8 @@ def _declare(L):
         "or_scene_set_box": (C.c_int, [P, C.c_int, P]),
         "or_scene_intersect": (None, [P, P, P, SZ, P, P, C.c_int]),
         "or_scene_occluded": (None, [P, P, P, SZ, P, P, C.c_int]),
+        "or_scene_intersect_ext": (None, [P, P, P, P, P, SZ, P, P, C.c_int]),
+        "or_scene_occluded_ext": (None, [P, P, P, P, P, SZ, P, P, C.c_int]),
         "or_spawn_shadows_pt": (SZ, [P, P, P, SZ, P, P, P, C.c_float, P, P, P]),
         "or_spawn_shadows_ao": (SZ, [P, P, P, P, SZ, C.c_int, P, P, P]),
         "or_shadow_slots": (C.c_int, [P]),
@@ -488,20 +490,31 @@ class Scene:
         """A domain owned elsewhere: listed by the domain query, no mesh."""
         assert lib().or_scene_set_box(self.h, i, _p(f32(box))) == 0
 
-    def intersect(self, org, d, nthreads=0):
+    @staticmethod
+    def _extent(x, n):
+        """Per-ray extent array (a scalar is broadcast), None -> NULL."""
+        if x is None:
+            return None
+        return f32(np.broadcast_to(np.asarray(x, np.float32), (n,)))
+
+    def intersect(self, org, d, nthreads=0, tnear=None, tfar=None):
+        """tnear / tfar: per-ray extents (None = 0.001 / +inf); the domain
+        list ignores them, see or_scene_intersect_ext."""
         n = len(org)
         hits = np.zeros(n, HIT_DTYPE)
         c = Counts()
-        lib().or_scene_intersect(self.h, _p(f32(org)), _p(f32(d)), n, _p(hits),
-                                 C.byref(c), int(nthreads))
+        lib().or_scene_intersect_ext(self.h, _p(f32(org)), _p(f32(d)),
+                                     _p(self._extent(tnear, n)), _p(self._extent(tfar, n)),
+                                     n, _p(hits), C.byref(c), int(nthreads))
         return hits, c.as_dict()
 
-    def occluded(self, org, d, nthreads=0):
+    def occluded(self, org, d, nthreads=0, tnear=None, tfar=None):
         n = len(org)
         o = np.zeros(n, np.uint8)
         c = Counts()
-        lib().or_scene_occluded(self.h, _p(f32(org)), _p(f32(d)), n, _p(o), C.byref(c),
-                                int(nthreads))
+        lib().or_scene_occluded_ext(self.h, _p(f32(org)), _p(f32(d)),
+                                    _p(self._extent(tnear, n)), _p(self._extent(tfar, n)),
+                                    n, _p(o), C.byref(c), int(nthreads))
         return o, c.as_dict()
 
 

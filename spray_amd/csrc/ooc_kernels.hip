@@ -659,12 +659,17 @@ __device__ __forceinline__ void ch_pair(const OocDomain& D, int slot, uint32_t p
   const DRay dr = make_dray(o4.x, o4.y, o4.z, d4.x, d4.y, d4.z);
   // the domain's own nearest hit with t <= the ray's best so far (ties at
   // that t included: the list position decides them); a pair whose domain
-  // starts beyond that t is dead and does not walk
-  const float tcur = k0 == kOocMissKey ? d4.w : __uint_as_float(uint32_t(k0 >> 32));
+  // starts beyond a hit already found is dead and does not walk.  The
+  // record's own tfar is no such cut: the domain list ignores the extents,
+  // and the entry t (the reference's unpadded box arithmetic) of a domain
+  // whose nearest triangle lies in its box face can round an ulp past a hit
+  // at t == tfar, which is accepted.
+  const bool found = k0 != kOocMissKey;
+  const float tcur = found ? __uint_as_float(uint32_t(k0 >> 32)) : d4.w;
   float te = 0.f;
   aabb_ref(boxes + 6 * D.domain, dr, te);
   Best best{tcur, 0xFFFFFFFFu, 0xFFFFFFFFu};
-  bool act = valid && !(te > tcur), hit = false;
+  bool act = valid && !(found && te > tcur), hit = false;
   if (__ballot(act))
     trace_tree_packet<false>(uniform_ptr(D.nodes), uniform_ptr(D.tris), uniform_ptr(D.prims), r,
                              o4.w, 0.f, best, act, hit, stack);
