@@ -342,16 +342,108 @@ int spray_rt_domains_isosurface(spray_rt_ctx_t ctx, int n, const int* slots,
  * faces_out uint32[*nfaces][3]). */
 int spray_rt_isosurface_host(const spray_rt_grid* grid, size_t* nverts, size_t* nfaces,
                              float* verts_out, float* vnormals_out, uint32_t* faces_out);
+/* ---- isosurfaces coloured by a second field through a colour map ---- */
+/* The colour map of one grid: entry i of an array parallel to the spray_rt_grid
+ * array.  field == NULL: the grid keeps the constant-colour rule (color_rgb /
+ * has_color), so one batch may mix mapped, constant-colour and colourless
+ * grids. */
+typedef struct spray_rt_grid_color {
+  const float* field;        /* the grid's dims and layout; device or host memory */
+  const uint32_t* table_rgb; /* [ntable] 0x00RRGGBB, host memory, copied verbatim */
+  int32_t ntable;            /* 1 .. 4096 */
+  float lo, hi;              /* lo < hi, both finite */
+} spray_rt_grid_color;
+/* The rule is fixed like the extraction's, in float
+ * without contraction: scale = float(ntable) / (hi - lo), evaluated once on
+ * the host (it must be a finite, normal float); a scalar g maps to
+ * table_rgb[idx], x = (g - lo) * scale, idx = !(x >= 0) ? 0 : (x >=
+ * float(ntable) ? ntable - 1 : int(x)) -- the nearest bin, clamped at both
+ * ends, no interpolation between entries (use a finer table).  The vertex on
+ * the lattice edge (a, b) at the extraction's t gets map(ga + t * (gb - ga)),
+ * ga / gb the colour field's samples at the edge's endpoints: a function of
+ * the lattice edge alone, like the position, so two grids that share a sample
+ * plane and the colour samples on it agree on the shared vertices' colours.  A
+ * slice is the isosurface of a plane-distance field coloured by the data.
+ *
+ * spray_rt_isosurface_mapped is spray_rt_isosurface plus colors[i] uint32
+ * [cap_verts[i]]: the mapped colour per vertex, color_rgb for a grid without a
+ * colour field.  verts / vnormals / colors / faces, or single entries of them,
+ * may be NULL independently (cap_verts is read where a grid has a per-vertex
+ * array, cap_faces where it has faces); all NULL only counts.  Positions,
+ * normals and faces are spray_rt_isosurface's, byte for byte.  With colors
+ * alone the call skips the position, normal and face work: the form that
+ * recolours a slot (spray_rt_domains_recolor below).
+ *
+ * Errors on top of spray_rt_isosurface's, all SPRAY_RT_ERR_ARG, naming the grid,
+ * before anything is written: a colour field with a NULL table, ntable out of
+ * range, lo >= hi or non-finite, a scale that is not a finite normal float, a
+ * non-finite colour sample (found by the count pass, reported at the call's one
+ * host read). */
+int spray_rt_isosurface_mapped(spray_rt_ctx_t ctx, int n, const spray_rt_grid* grids,
+                               const spray_rt_grid_color* gcolors, float* const* verts,
+                               float* const* vnormals, uint32_t* const* colors,
+                               uint32_t* const* faces, const size_t* cap_verts,
+                               const size_t* cap_faces, size_t* nverts_out, size_t* nfaces_out);
+/* spray_rt_domains_isosurface with mapped colours: a slot carries colours when
+ * its grid has a colour field or has_color.  The same host reads (at most
+ * three) and the same all-or-nothing failure; the errors of
+ * spray_rt_isosurface_mapped on top.  Not for use while lanes run. */
+int spray_rt_domains_isosurface_mapped(spray_rt_ctx_t ctx, int n, const int* slots,
+                                       const spray_rt_grid* grids,
+                                       const spray_rt_grid_color* gcolors, int with_normals,
+                                       float* d_bounds, size_t* nfaces_out);
+/* Host-only restatement (no GPU; the fields are host memory): as
+ * spray_rt_isosurface_host, plus colors_out uint32[*nverts].  gcolor may be
+ * NULL. */
+int spray_rt_isosurface_mapped_host(const spray_rt_grid* grid, const spray_rt_grid_color* gcolor,
+                                    size_t* nverts, size_t* nfaces, float* verts_out,
+                                    float* vnormals_out, uint32_t* colors_out,
+                                    uint32_t* faces_out);
+/* The map alone, for meshes that carry per-vertex data of their own:
+ * colors_out[i] = map(scalars[i]) for n scalars on the context's stream.
+ * scalars: device or host memory (host: staged); colors_out: device memory.
+ * SPRAY_RT_ERR_ARG for a bad map or a non-finite scalar (one status-word read:
+ * the call synchronises; colors_out is then unspecified). */
+int spray_rt_colormap_apply(spray_rt_ctx_t ctx, const float* scalars, size_t n,
+                            const uint32_t* table_rgb, int32_t ntable, float lo, float hi,
+                            uint32_t* colors_out);
+/* Host-only restatement of spray_rt_colormap_apply (no GPU). */
+int spray_rt_colormap_host(const float* scalars, size_t n, const uint32_t* table_rgb,
+                           int32_t ntable, float lo, float hi, uint32_t* colors_out);
+/* New per-vertex colours for n resident slots in one batched call, ordered
+ * after the queued work on the context's stream and before the next query:
+ * colors_rgb[i] uint32 [nverts[i]], device or host memory (host: staged, and
+ * the call returns with the work completed).  Only the slots' colour arrays
+ * are written: trees, records, faces, normals and refit metadata keep their
+ * bytes, and a later spray_rt_domains_refit keeps the new colours.
+ *
+ * All validation happens on the host before anything is enqueued, so a failed
+ * call leaves every slot as it was and the call reads no device state:
+ * SPRAY_RT_ERR_ARG for an unloaded slot, a slot listed twice, a slot uploaded or
+ * built without colours (a slot is one allocation: a colour array cannot be
+ * added), a NULL pointer, or nverts[i] different from the slot's.
+ * spray_rt_last_error names the slot.  Not for use while lanes run.
+ *
+ * Recolouring an isosurface slot (another colour field, another table) is
+ * spray_rt_isosurface_mapped with colors alone on the same grids, then this
+ * call with those device pointers: a colour pass instead of a build.  That
+ * relies on the geometry field and the isovalue being the ones the slot was
+ * extracted from; the nverts check catches most mismatches, not all. */
+int spray_rt_domains_recolor(spray_rt_ctx_t ctx, int n, const int* slots,
+                             const uint32_t* const* colors_rgb, const size_t* nverts);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes
- * for QNODES4 and QGRID, slots without normals 0 for NORMALS. */
+ * for QNODES4 and QGRID, slots without normals 0 for NORMALS, slots without
+ * colours 0 for COLORS. */
 #define SPRAY_RT_SLOT_NODES 0   /* BvhNode[]  */
 #define SPRAY_RT_SLOT_TRIS 1    /* float[ntris][12] */
 #define SPRAY_RT_SLOT_PRIMS 2   /* uint32[ntris] leaf order -> face */
 #define SPRAY_RT_SLOT_QNODES4 3 /* QNode4[], index order */
 #define SPRAY_RT_SLOT_QGRID 4   /* float[6] base, scale */
 #define SPRAY_RT_SLOT_NORMALS 5 /* float[nverts][3] */
+#define SPRAY_RT_SLOT_COLORS 6  /* uint32[nverts] */
+#define SPRAY_RT_SLOT_FACES 7   /* uint32[ntris][3] */
 int spray_rt_slot_export(spray_rt_ctx_t ctx, int slot, int what, void* out, size_t cap_bytes,
                          size_t* nbytes);
 /* SAH cost of the slot's current BVH2, so a caller can tell when refits have

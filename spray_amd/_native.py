@@ -84,6 +84,12 @@ SIGNATURES = {
     "spray_rt_isosurface": (I, [P, I, P, P, P, P, P, P, P, P]),
     "spray_rt_domains_isosurface": (I, [P, I, P, P, I, P, P]),
     "spray_rt_isosurface_host": (I, [P, P, P, P, P, P]),
+    "spray_rt_isosurface_mapped": (I, [P, I, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_isosurface_mapped": (I, [P, I, P, P, P, I, P, P]),
+    "spray_rt_isosurface_mapped_host": (I, [P, P, P, P, P, P, P, P]),
+    "spray_rt_colormap_apply": (I, [P, P, SZ, P, C.c_int32, C.c_float, C.c_float, P]),
+    "spray_rt_colormap_host": (I, [P, SZ, P, C.c_int32, C.c_float, C.c_float, P]),
+    "spray_rt_domains_recolor": (I, [P, I, P, P, P]),
     "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
     "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),

@@ -31,7 +31,7 @@ SOURCES = ["rt_kernels.hip", "ooc_kernels.hip", "frame_kernels.hip", "insitu_ker
 HEADERS = ["rt_common.h", "rt_device.h", "shade_device.h", "cam_device.h", "rt_kernels.h", "rt_ctx.h",
            "bvh_build.h", "scene_host.h", "insitu_kernels.h", "footprint.h", "refit_common.h",
            "refit_kernels.h", "build_common.h", "build_kernels.h", "iso_common.h",
-           "iso_kernels.h", "job_arena.h", "block_scan.h"]
+           "iso_kernels.h", "job_arena.h", "block_scan.h", "color_common.h"]
 PUBLIC = [os.path.join(ROOT, "include", h) for h in ("spray_rt.h", "spray_scene.h")]
 
 

@@ -25,6 +25,7 @@ namespace spray_rt {
 namespace iso {
 
 constexpr uint32_t kBadSample = 1;  // status bit of a grid: a non-finite sample
+constexpr uint32_t kBadColor = 2;   // ... a non-finite sample of its colour field
 
 // The extraction numbers per block of kIsoBlock consecutive points; a point's
 // code word holds its crossing-edge mask and its exclusive vertex / face

@@ -313,6 +313,14 @@ int spray_rt_slot_export(spray_rt_ctx_t c, int slot, int what, void* out, size_t
       src = sh.desc.normals;
       bytes = sh.desc.normals ? 3 * size_t(sh.desc.nverts) * sizeof(float) : 0;
       break;
+    case SPRAY_RT_SLOT_COLORS:
+      src = sh.desc.colors;
+      bytes = sh.desc.colors ? size_t(sh.desc.nverts) * sizeof(uint32_t) : 0;
+      break;
+    case SPRAY_RT_SLOT_FACES:
+      src = sh.desc.faces;
+      bytes = 3 * size_t(sh.desc.ntris) * sizeof(uint32_t);
+      break;
     default:
       return fail(c, SPRAY_RT_ERR_ARG, "slot export: unknown array %d", what);
   }

@@ -412,7 +412,8 @@ int spray_rt_destroy(spray_rt_ctx_t c) {
                   c->d_sah, c->d_sort, c->d_isomesh};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
-  for (JobArena* a : {&c->refit, &c->build, &c->iso}) arena_release(a);
+  for (JobArena* a : {&c->refit, &c->build, &c->iso, &c->recolor}) arena_release(a);
+  if (c->recolor_copied) (void)hipEventDestroy(c->recolor_copied);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
   delete c;

@@ -90,6 +90,8 @@ struct spray_rt_ctx {
   spray_rt::detail::JobArena refit;  // job table, status words | grids, scratch image
   spray_rt::detail::JobArena build;  // job tables, records | grids, keys, scratch images
   spray_rt::detail::JobArena iso;    // job tables, records | staged fields, per-point scratch
+  spray_rt::detail::JobArena recolor;  // job table | staged colours (spray_rt_domains_recolor)
+  hipEvent_t recolor_copied = nullptr;  // the last recolor's job table has left pinned memory
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;

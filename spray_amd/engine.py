@@ -17,6 +17,7 @@ from ._native import (HIT_DTYPE, INVALID_ID, RAY_DTYPE, RTC_ISECT_DTYPE, BsdfRec
 
 __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_rays",
            "bvh_refit_host", "bvh_build_device_host", "isosurface_host",
+           "isosurface_mapped_host", "colormap_host", "SLOT_COLORS", "SLOT_FACES",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
            "HIT_DTYPE", "RTC_ISECT_DTYPE", "INVALID_ID", "SprayRtError"]
@@ -199,6 +200,103 @@ def isosurface_host(values, origin, spacing, iso, normals=True):
     return v, n, f
 
 
+class _GridColor(C.Structure):
+    """spray_rt_grid_color."""
+    _fields_ = [("field", C.c_void_p), ("table_rgb", C.c_void_p), ("ntable", C.c_int32),
+                ("lo", C.c_float), ("hi", C.c_float)]
+
+
+assert C.sizeof(_GridColor) == 32
+
+# spray_rt_slot_export's arrays beyond RtContext.SLOT_NORMALS
+SLOT_COLORS, SLOT_FACES = 6, 7
+
+
+def _cmap_args(cmap):
+    """(table uint32[n], lo, hi) -> (table array, its address, n, lo, hi)."""
+    table, lo, hi = cmap
+    t = np.ascontiguousarray(table, np.uint32).reshape(-1)
+    return t, (t.ctypes.data if t.size else None), int(t.size), float(lo), float(hi)
+
+
+def _fills_done():
+    """Tensors created just now are zero-filled on torch's current stream; the
+    context's stream is not ordered after it, so the fills complete first."""
+    import torch
+    torch.cuda.current_stream().synchronize()
+
+
+def _grid_color_table(grids):
+    """The spray_rt_grid_color array parallel to _grid_table(grids): dicts may
+    carry "cfield" (float32 [nz, ny, nx], numpy or a torch tensor on the GPU)
+    and "cmap" = (table uint32[n], lo, hi); other grids keep their constant
+    colour -> (array, keepalive)."""
+    arr = (_GridColor * max(len(grids), 1))()
+    keep = []
+    for g, rec in zip(grids, arr):
+        cf = g.get("cfield") if isinstance(g, dict) else None
+        if cf is None:
+            continue
+        values = g["values"]
+        if hasattr(cf, "data_ptr"):
+            if cf.element_size() != 4 or not cf.is_floating_point():
+                raise TypeError("isosurface: fields are float32")
+        else:
+            cf = np.ascontiguousarray(cf, np.float32)
+        if tuple(cf.shape) != tuple(values.shape):
+            raise ValueError("isosurface: a colour field has its grid's shape")
+        a, k = _addr(cf)
+        keep.append(k)
+        rec.field = a
+        if g.get("cmap") is not None:
+            t, rec.table_rgb, rec.ntable, rec.lo, rec.hi = _cmap_args(g["cmap"])
+            keep.append(t)
+    return arr, keep
+
+
+def isosurface_mapped_host(values, origin, spacing, iso, cfield=None, cmap=None, normals=True,
+                           color=None):
+    """spray_rt_isosurface_mapped_host (no GPU): isosurface_host plus the
+    per-vertex colours, mapped from cfield through cmap = (table, lo, hi) or the
+    constant color -> (verts, normals or None, colors uint32 [nv], faces)."""
+    g = dict(values=np.ascontiguousarray(values, np.float32), origin=origin, spacing=spacing,
+             iso=iso, color=color, cfield=cfield, cmap=cmap)
+    arr, keep = _grid_table([g])
+    carr, ckeep = _grid_color_table([g])
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_isosurface_mapped_host(C.addressof(arr), C.addressof(carr), C.byref(nv),
+                                               C.byref(nf), *outs)
+        if rc != 0:
+            e = SprayRtError("isosurface_mapped_host failed (%d)" % rc)
+            e.code = rc
+            raise e
+
+    call(None, None, None, None)
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals else None
+    c = np.zeros(nv.value, np.uint32)
+    f = np.zeros((nf.value, 3), np.uint32)
+    call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, f.ctypes.data)
+    return v, n, c, f
+
+
+def colormap_host(scalars, table, lo, hi):
+    """spray_rt_colormap_host (no GPU): table[bin] of every scalar -> uint32
+    array of scalars' shape."""
+    x = np.ascontiguousarray(scalars, np.float32)
+    t, ta, nt, lo, hi = _cmap_args((table, lo, hi))
+    out = np.zeros(x.shape, np.uint32)
+    rc = lib().spray_rt_colormap_host(x.ctypes.data, x.size, ta, nt, lo, hi, out.ctypes.data)
+    if rc != 0:
+        e = SprayRtError("colormap_host failed (%d)" % rc)
+        e.code = rc
+        raise e
+    return out
+
+
 def host_parse_scene(desc, ply_path=""):
     """Scene file -> (boxes [n,6], lights [nl,7]) without touching the GPU
     (spray_host_parse_scene)."""
@@ -332,7 +430,9 @@ class RtContext:
 
     # ---- moving geometry ----
     SLOT_NODES, SLOT_TRIS, SLOT_PRIMS, SLOT_QNODES4, SLOT_QGRID, SLOT_NORMALS = range(6)
-    _SLOT_DTYPES = (np.uint8, np.float32, np.uint32, np.uint8, np.float32, np.float32)
+    SLOT_COLORS, SLOT_FACES = SLOT_COLORS, SLOT_FACES
+    _SLOT_DTYPES = (np.uint8, np.float32, np.uint32, np.uint8, np.float32, np.float32,
+                    np.uint32, np.uint32)
 
     def _bounds_out(self, bounds, n):
         """Where a batched slot call writes its [n, 6] boxes: a new GPU tensor
@@ -514,10 +614,147 @@ class RtContext:
             return out[:n].cpu().numpy()
         return out
 
+    # ---- colour maps ----
+    def isosurface_mapped(self, grids, normals=True, capacity=None, colors_only=False):
+        """spray_rt_isosurface_mapped: isosurface() with per-vertex colours,
+        mapped from a grid's "cfield" through its "cmap" (see
+        _grid_color_table) or its constant colour -> [(verts, normals or None,
+        colors int32 [nv] holding the 0x00RRGGBB bits, faces)] as GPU tensors.
+        colors_only: the colours alone (the other entries are None), without
+        the position, normal and face work -- what recolor_domains takes.
+        Enqueued on the context's stream: sync() before reading the tensors on
+        another stream."""
+        import torch
+        n = len(grids)
+        arr, keep = _grid_table(grids)
+        carr, ckeep = _grid_color_table(grids)
+        m = max(n, 1)
+        nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        L = lib()
+        if capacity is None:
+            self._check(L.spray_rt_isosurface_mapped(self.h, n, arr, carr, None, None, None, None,
+                                                     None, None, nv, nf), "isosurface_mapped")
+            caps = [(nv[i], nf[i]) for i in range(n)]
+        else:
+            caps = [(int(capacity[0]), int(capacity[1]))] * n
+        dev = "cuda:%d" % self._device
+        full = not colors_only
+        # zeroed, one element at least: a buffer a failed call must not touch
+        v = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) if full else None
+             for cv, _ in caps]
+        nr = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev)
+              if full and normals else None for cv, _ in caps]
+        col = [torch.zeros(max(cv, 1), dtype=torch.int32, device=dev) for cv, _ in caps]
+        f = [torch.zeros((max(cf, 1), 3), dtype=torch.int32, device=dev) if full else None
+             for _, cf in caps]
+
+        def ptrs(xs):
+            if all(x is None for x in xs):
+                return None
+            return (C.c_void_p * m)(*[None if x is None else x.data_ptr() for x in xs])
+
+        _fills_done()
+        try:
+            self._check(L.spray_rt_isosurface_mapped(
+                self.h, n, arr, carr, ptrs(v), ptrs(nr), ptrs(col), ptrs(f),
+                (C.c_size_t * m)(*[c[0] for c in caps]),
+                (C.c_size_t * m)(*[c[1] for c in caps]) if full else None, nv, nf),
+                "isosurface_mapped")
+        except SprayRtError as e:
+            e.counts = [(nv[i], nf[i]) for i in range(n)]
+            e.buffers = tuple(b for b in (v, nr, col, f) if b[0] is not None) if n else ()
+            raise
+        cut = lambda x, k: None if x is None else x[:k]
+        return [(cut(v[i], nv[i]), cut(nr[i], nv[i]), col[i][:nv[i]], cut(f[i], nf[i]))
+                for i in range(n)]
+
+    def isosurface_domains_mapped(self, slots, grids, normals=True, bounds=None):
+        """spray_rt_domains_isosurface_mapped: isosurface_domains() with the
+        colours of isosurface_mapped()."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(grids) != n:
+            e = SprayRtError("isosurface_domains_mapped: %d slots, %d grids" % (n, len(grids)))
+            e.code = -1
+            raise e
+        arr, keep = _grid_table(grids)
+        carr, ckeep = _grid_color_table(grids)
+        m = max(n, 1)
+        sl = (C.c_int * m)(*slots)
+        out = self._bounds_out(bounds, n)
+        b, k = _addr(out)
+        nf = (C.c_size_t * m)()
+        self._check(lib().spray_rt_domains_isosurface_mapped(
+            self.h, n, sl, arr, carr, 1 if normals else 0, b, nf), "domains_isosurface_mapped")
+        for s in slots:
+            self._nverts.pop(s, None)  # the vertex count is the extraction's
+        if bounds is True:
+            self.sync()
+            return out[:n].cpu().numpy()
+        return out
+
+    def recolor_domains(self, slots, colors):
+        """spray_rt_domains_recolor: new per-vertex colours for resident slots
+        that carry colours.  colors[i]: uint32 [nverts] numpy arrays (staged; the
+        call is synchronous) or 32-bit torch tensors on the GPU (enqueued)."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(colors) != n:
+            e = SprayRtError("recolor_domains: %d slots, %d colour arrays" % (n, len(colors)))
+            e.code = -1
+            raise e
+        keep, ptr, cnt = [], [], []
+        for x in colors:
+            if x is None:
+                ptr.append(None)
+                cnt.append(0)
+                continue
+            if not hasattr(x, "data_ptr"):
+                x = np.ascontiguousarray(x, np.uint32)
+                cnt.append(x.size)
+            elif x.element_size() != 4:
+                raise TypeError("recolor_domains: tensors hold 32-bit elements")
+            else:
+                cnt.append(x.numel())
+            a, k = _addr(x)
+            keep.append(k)
+            ptr.append(a)
+        m = max(n, 1)
+        self._check(lib().spray_rt_domains_recolor(self.h, n, (C.c_int * m)(*slots),
+                                                   (C.c_void_p * m)(*ptr), (C.c_size_t * m)(*cnt)),
+                    "domains_recolor")
+
+    def colormap_apply(self, scalars, cmap, out=None):
+        """spray_rt_colormap_apply: cmap = (table uint32[n], lo, hi) over
+        scalars (float32, numpy or a GPU tensor) -> int32 GPU tensor holding the
+        0x00RRGGBB bits (out, if given: a 32-bit GPU tensor of that many
+        elements).  Synchronises."""
+        import torch
+        if hasattr(scalars, "data_ptr"):
+            if scalars.element_size() != 4 or not scalars.is_floating_point():
+                raise TypeError("colormap_apply: scalars are float32")
+            count = scalars.numel()
+        else:
+            scalars = np.ascontiguousarray(scalars, np.float32)
+            count = scalars.size
+        if out is None:
+            out = torch.zeros(count, dtype=torch.int32, device="cuda:%d" % self._device)
+            _fills_done()
+        elif out.numel() != count or out.element_size() != 4:
+            raise ValueError("colormap_apply: out holds one 32-bit element per scalar")
+        t, ta, nt, lo, hi = _cmap_args(cmap)
+        a, k = _addr(scalars)
+        o, ko = _addr(out)
+        self._check(lib().spray_rt_colormap_apply(self.h, a, count, ta, nt, lo, hi, o),
+                    "colormap_apply")
+        return out
+
     def slot_export(self, slot, what):
         """One array of a resident slot as numpy: SLOT_NODES / SLOT_QNODES4 as
         uint8 [n, 64] (the 64-B node records), SLOT_TRIS float32 [ntris, 12],
-        SLOT_PRIMS uint32, SLOT_QGRID float32 [6], SLOT_NORMALS float32 [nverts, 3]."""
+        SLOT_PRIMS uint32, SLOT_QGRID float32 [6], SLOT_NORMALS float32 [nverts, 3],
+        SLOT_COLORS uint32 [nverts] (empty for a slot without colours), SLOT_FACES
+        uint32 [ntris, 3]."""
         nb = C.c_size_t()
         self._check(lib().spray_rt_slot_export(self.h, int(slot), int(what), None, 0,
                                                C.byref(nb)), "slot_export")
@@ -527,7 +764,7 @@ class RtContext:
                                                    out.nbytes, C.byref(nb)), "slot_export")
         out = out.view(self._SLOT_DTYPES[int(what)])
         shape = {self.SLOT_NODES: (-1, 64), self.SLOT_QNODES4: (-1, 64), self.SLOT_TRIS: (-1, 12),
-                 self.SLOT_NORMALS: (-1, 3)}.get(int(what))
+                 self.SLOT_NORMALS: (-1, 3), self.SLOT_FACES: (-1, 3)}.get(int(what))
         return out.reshape(shape) if shape else out
 
     def slot_sah(self, slot):
