@@ -431,6 +431,95 @@ int spray_rt_colormap_host(const float* scalars, size_t n, const uint32_t* table
  * extracted from; the nverts check catches most mismatches, not all. */
 int spray_rt_domains_recolor(spray_rt_ctx_t ctx, int n, const int* slots,
                              const uint32_t* const* colors_rgb, const size_t* nverts);
+/* ---- isosurfaces of unstructured tetrahedral meshes ---- */
+/* One tetrahedral mesh with a scalar per point and the isovalue to contour it
+ * at: what a finite-element or finite-volume code leaves in HBM. */
+typedef struct spray_rt_tetmesh {
+  const float*    points;        /* [npoints][3]; device or host memory */
+  const uint32_t* tets;          /* [ntets][4] point indices; device or host */
+  const float*    values;        /* [npoints], the field to contour */
+  const float*    point_normals; /* optional [npoints][3], unnormalised, e.g. the
+                                    negated gradient; NULL: the mesh has no normals */
+  size_t   npoints, ntets;
+  float    isovalue;
+  uint32_t color_rgb;            /* as spray_rt_grid */
+  int32_t  has_color;
+} spray_rt_tetmesh;
+/* The rule is fixed like the grid extraction's, so that the kernels and the
+ * host restatement agree byte for byte, in float
+ * without contraction.  A point is inside when f >= isovalue.  There is one
+ * vertex per distinct unordered point pair {a, b}, a < b by point index, that
+ * is an edge of at least one tetrahedron and whose endpoints differ in sign:
+ * t = (isovalue - f[a]) / (f[b] - f[a]), position p[a] + t * (p[b] - p[a]) per
+ * axis, normal and colour scalar interpolated the same way, colour
+ * map(g[a] + t * (g[b] - g[a])) with spray_rt_grid_color's rule (its field is
+ * [npoints] here) or color_rgb -- all a function of the pair alone, so the
+ * mesh is watertight, and two meshes that share points with equal
+ * coordinates, samples and relative index order agree bit for bit on the
+ * shared vertices.  Vertices are ascending by (a << 32) | b.  Faces come per
+ * tetrahedron in input order, then triangle 0..1: marching tetrahedra with the
+ * tet's four listed points as the walk, and the orientation from the
+ * geometry, not from the caller's vertex order: odd when det = dot(cross(p1 -
+ * p0, p2 - p0), p3 - p0) < 0, evaluated term by term in float, left to right
+ * (det == 0 and NaN count as even), so a mesh of mixed tet orientations still
+ * gives Ng = (v0 - v1) x (v2 - v0) pointing toward decreasing values.  A
+ * sliver whose float det has the wrong sign flips its one or two triangles.
+ * A sample equal to the isovalue gives t of 0 or 1 and possibly zero-area
+ * triangles; they are kept.  A tet that lists a point twice never crosses on
+ * that pair; duplicate tets give duplicate faces.  No atomic and no hash
+ * decides an index: two runs give the same bytes.
+ *
+ * spray_rt_tet_isosurface extracts n meshes into the caller's device buffers
+ * in one batched call on the context's stream, with the argument shapes of
+ * spray_rt_isosurface_mapped: gcolors may be NULL; verts / vnormals / colors /
+ * faces, or single entries of them, may be NULL independently; all NULL only
+ * counts.  Two host reads, however many meshes: status and the instance /
+ * face totals after the count pass, the vertex counts after the sort.  A
+ * capacity that is too small gives SPRAY_RT_ERR_LIMIT with the counts
+ * reported and no buffer written.
+ *
+ * SPRAY_RT_ERR_ARG, before anything is written and naming the mesh: a NULL
+ * pointer (ntets == 0 is allowed, reads nothing and gives the empty surface),
+ * a non-finite isovalue, a bad colour map (spray_rt_isosurface_mapped's
+ * checks), vnormals[i] non-NULL for a mesh without point_normals, a point
+ * index >= npoints, or a non-finite value among what the call reads of a
+ * point some tet references: coordinates, sample, colour sample of a mapped
+ * mesh, normal where normals are written (points no tet references are never
+ * read).  SPRAY_RT_ERR_LIMIT: ntets >= 2^29, npoints >= 2^32, or 2^32 or more
+ * crossing (tet, edge) instances in one call. */
+int spray_rt_tet_isosurface(spray_rt_ctx_t ctx, int n, const spray_rt_tetmesh* meshes,
+                            const spray_rt_grid_color* gcolors, float* const* verts,
+                            float* const* vnormals, uint32_t* const* colors,
+                            uint32_t* const* faces, const size_t* cap_verts,
+                            const size_t* cap_faces, size_t* nverts_out, size_t* nfaces_out);
+/* Meshes in, resident slots out: the extraction into context scratch at the
+ * exact sizes, then the device build of spray_rt_domains_build on those device
+ * arrays.  Afterwards slots[i] is a slot of spray_rt_domains_build of the
+ * extracted mesh of meshes[i] (with its normals if with_normals and the mesh
+ * has point_normals, its colours if it is mapped or has_color), byte for byte,
+ * for every call that takes a slot, a later spray_rt_domains_refit and
+ * spray_rt_domains_recolor included.  At most four host reads per call (the
+ * extraction's two and the build's two).  A failed call leaves every slot as
+ * it was; errors as spray_rt_tet_isosurface, plus a bad slot or a slot listed
+ * twice and the build's limits.  Not for use while lanes run. */
+int spray_rt_domains_tet_isosurface(spray_rt_ctx_t ctx, int n, const int* slots,
+                                    const spray_rt_tetmesh* meshes,
+                                    const spray_rt_grid_color* gcolors, int with_normals,
+                                    float* d_bounds, size_t* nfaces_out);
+/* Where the last tet extraction of the context spent its time: out_ms[0..2]
+ * wall clock from entry to host read 1, from there to host read 2, from there
+ * to the end of the vertex and face passes' enqueue; out_ms[3] the device time
+ * of the segmented sort (HIP events on the context's stream), recorded only
+ * while timing is on (spray_rt_tet_set_timing; off by default), else 0. */
+int spray_rt_tet_set_timing(spray_rt_ctx_t ctx, int on);
+int spray_rt_tet_phase_times(spray_rt_ctx_t ctx, double out_ms[4]);
+/* Host-only restatement (no GPU; every array is host memory): the arrays the
+ * kernels write, byte for byte.  *nverts / *nfaces are reported where the
+ * input is valid; any output may be NULL (as spray_rt_isosurface_mapped_host);
+ * vnormals_out needs point_normals.  gcolor may be NULL. */
+int spray_rt_tet_isosurface_host(const spray_rt_tetmesh* mesh, const spray_rt_grid_color* gcolor,
+                                 size_t* nverts, size_t* nfaces, float* verts_out,
+                                 float* vnormals_out, uint32_t* colors_out, uint32_t* faces_out);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes

@@ -58,6 +58,16 @@ class ShaderRec(C.Structure):
 assert C.sizeof(LightRec) == 28 and C.sizeof(BsdfRec) == 16
 assert C.sizeof(ShaderRec) == 32 + 28 * MAX_LIGHTS
 
+
+class TetMesh(C.Structure):
+    """spray_rt_tetmesh."""
+    _fields_ = [("points", C.c_void_p), ("tets", C.c_void_p), ("values", C.c_void_p),
+                ("point_normals", C.c_void_p), ("npoints", C.c_size_t), ("ntets", C.c_size_t),
+                ("isovalue", C.c_float), ("color_rgb", C.c_uint32), ("has_color", C.c_int32)]
+
+
+assert C.sizeof(TetMesh) == 64
+
 # every symbol the public headers declare: (restype, argtypes)
 P = C.c_void_p
 SZ = C.c_size_t
@@ -90,6 +100,11 @@ SIGNATURES = {
     "spray_rt_colormap_apply": (I, [P, P, SZ, P, C.c_int32, C.c_float, C.c_float, P]),
     "spray_rt_colormap_host": (I, [P, SZ, P, C.c_int32, C.c_float, C.c_float, P]),
     "spray_rt_domains_recolor": (I, [P, I, P, P, P]),
+    "spray_rt_tet_isosurface": (I, [P, I, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_tet_isosurface": (I, [P, I, P, P, P, I, P, P]),
+    "spray_rt_tet_isosurface_host": (I, [P, P, P, P, P, P, P, P]),
+    "spray_rt_tet_set_timing": (I, [P, I]),
+    "spray_rt_tet_phase_times": (I, [P, P]),
     "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
     "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),

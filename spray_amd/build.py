@@ -27,11 +27,13 @@ ARCH = os.environ.get("SPRAY_AMD_ARCH", "gfx950")
 SOURCES = ["rt_kernels.hip", "ooc_kernels.hip", "frame_kernels.hip", "insitu_kernels.hip",
            "rt_api.cpp", "ooc.cpp", "frame.cpp", "insitu.cpp", "bvh_build.cpp", "scene_host.cpp",
            "footprint.cpp", "refit_kernels.hip", "refit.cpp", "build_kernels.hip",
-           "build_device.cpp", "iso_kernels.hip", "isosurface.cpp"]
+           "build_device.cpp", "iso_kernels.hip", "isosurface.cpp", "tet_kernels.hip",
+           "tet_isosurface.cpp"]
 HEADERS = ["rt_common.h", "rt_device.h", "shade_device.h", "cam_device.h", "rt_kernels.h", "rt_ctx.h",
            "bvh_build.h", "scene_host.h", "insitu_kernels.h", "footprint.h", "refit_common.h",
            "refit_kernels.h", "build_common.h", "build_kernels.h", "iso_common.h",
-           "iso_kernels.h", "job_arena.h", "block_scan.h", "color_common.h"]
+           "iso_kernels.h", "job_arena.h", "block_scan.h", "color_common.h", "tet_common.h",
+           "tet_kernels.h"]
 PUBLIC = [os.path.join(ROOT, "include", h) for h in ("spray_rt.h", "spray_scene.h")]
 
 

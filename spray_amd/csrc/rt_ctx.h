@@ -92,6 +92,15 @@ struct spray_rt_ctx {
   spray_rt::detail::JobArena iso;    // job tables, records | staged fields, per-point scratch
   spray_rt::detail::JobArena recolor;  // job table | staged colours (spray_rt_domains_recolor)
   hipEvent_t recolor_copied = nullptr;  // the last recolor's job table has left pinned memory
+  spray_rt::detail::JobArena tet;  // job tables, records | staged mesh arrays, per-tet scratch
+  void* d_tetinst = nullptr;       // tet isosurface: the per-instance scratch (keys, ids)
+  size_t tetinst_cap = 0;
+  // spray_rt_tet_set_timing / spray_rt_tet_phase_times: wall clock to host
+  // read 1, to host read 2, to the end of the extraction's enqueue; the sort's
+  // device time between the two events
+  bool tet_timing = false;
+  double tet_ms[4] = {};
+  hipEvent_t tet_ev[2] = {nullptr, nullptr};
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;

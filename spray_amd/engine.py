@@ -13,11 +13,12 @@ import ctypes as C
 import numpy as np
 
 from ._native import (HIT_DTYPE, INVALID_ID, RAY_DTYPE, RTC_ISECT_DTYPE, BsdfRec,
-                      SprayRtError, lib)
+                      SprayRtError, TetMesh, lib)
 
 __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_rays",
            "bvh_refit_host", "bvh_build_device_host", "isosurface_host",
-           "isosurface_mapped_host", "colormap_host", "SLOT_COLORS", "SLOT_FACES",
+           "isosurface_mapped_host", "colormap_host", "tet_isosurface_host", "SLOT_COLORS",
+           "SLOT_FACES",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
            "HIT_DTYPE", "RTC_ISECT_DTYPE", "INVALID_ID", "SprayRtError"]
@@ -295,6 +296,97 @@ def colormap_host(scalars, table, lo, hi):
         e.code = rc
         raise e
     return out
+
+
+def _tet_array(x, dtype, cols, what):
+    """x as the [n, cols] (cols 0: [n]) 32-bit array the engine reads: a numpy
+    array of dtype or a torch tensor on the GPU -> (array, rows)."""
+    if hasattr(x, "data_ptr"):
+        if x.element_size() != 4 or x.is_floating_point() != (dtype == np.float32):
+            raise TypeError("tet_isosurface: %s are %s" % (what, np.dtype(dtype).name))
+        size = x.numel()
+    else:
+        x = np.ascontiguousarray(x, dtype)
+        size = x.size
+    if cols and size % cols:
+        raise ValueError("tet_isosurface: %s are a [n, %d] array" % (what, cols))
+    return x, size // max(cols, 1)
+
+
+def _tet_table(meshes):
+    """Dicts with "points" (float32 [np, 3]), "tets" (uint32 or int32 [nt, 4]),
+    "values" (float32 [np]), "iso" and optionally "normals" (float32 [np, 3]),
+    "color", "cfield" (float32 [np]) with "cmap" = (table uint32[n], lo, hi) ->
+    (spray_rt_tetmesh array, spray_rt_grid_color array, keepalive).  Arrays are
+    numpy arrays or torch tensors on the GPU."""
+    arr = (TetMesh * max(len(meshes), 1))()
+    carr = (_GridColor * max(len(meshes), 1))()
+    keep = []
+
+    def put(x):
+        a, k = _addr(x)
+        keep.append(k)
+        return a
+
+    for m, rec, crec in zip(meshes, arr, carr):
+        tets = m["tets"]
+        if not hasattr(tets, "data_ptr"):
+            tets = np.asarray(tets)
+            tets = tets.view(np.uint32) if tets.dtype == np.int32 else tets
+        points, npts = _tet_array(m["points"], np.float32, 3, "points")
+        tets, ntets = _tet_array(tets, np.uint32, 4, "tets")
+        values, nval = _tet_array(m["values"], np.float32, 0, "values")
+        if nval != npts:
+            raise ValueError("tet_isosurface: one value per point")
+        rec.points, rec.tets, rec.values = put(points), put(tets), put(values)
+        rec.npoints, rec.ntets = npts, ntets
+        if m.get("normals") is not None:
+            nrm, nn = _tet_array(m["normals"], np.float32, 3, "normals")
+            if nn != npts:
+                raise ValueError("tet_isosurface: one normal per point")
+            rec.point_normals = put(nrm)
+        rec.isovalue = float(m["iso"])
+        color = m.get("color")
+        rec.has_color = 0 if color is None else 1
+        rec.color_rgb = 0 if color is None else int(color)
+        if m.get("cfield") is not None:
+            cf, nc = _tet_array(m["cfield"], np.float32, 0, "colour samples")
+            if nc != npts:
+                raise ValueError("tet_isosurface: one colour sample per point")
+            crec.field = put(cf)
+            if m.get("cmap") is not None:
+                t, crec.table_rgb, crec.ntable, crec.lo, crec.hi = _cmap_args(m["cmap"])
+                keep.append(t)
+    return arr, carr, keep
+
+
+def tet_isosurface_host(points, tets, values, iso, normals=None, cfield=None, cmap=None,
+                        color=None):
+    """spray_rt_tet_isosurface_host (no GPU): the mesh RtContext.tet_isosurface
+    extracts from a tetrahedral mesh (see _tet_table; numpy arrays) -> (verts
+    float32 [nv, 3], normals float32 [nv, 3] or None without point normals,
+    colors uint32 [nv], faces uint32 [nf, 3])."""
+    m = dict(points=points, tets=tets, values=values, iso=iso, normals=normals, cfield=cfield,
+             cmap=cmap, color=color)
+    arr, carr, keep = _tet_table([m])
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_tet_isosurface_host(C.addressof(arr), C.addressof(carr), C.byref(nv),
+                                            C.byref(nf), *outs)
+        if rc != 0:
+            e = SprayRtError("tet_isosurface_host failed (%d)" % rc)
+            e.code = rc
+            raise e
+
+    call(None, None, None, None)
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals is not None else None
+    c = np.zeros(nv.value, np.uint32)
+    f = np.zeros((nf.value, 3), np.uint32)
+    call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, f.ctypes.data)
+    return v, n, c, f
 
 
 def host_parse_scene(desc, ply_path=""):
@@ -748,6 +840,96 @@ class RtContext:
         self._check(lib().spray_rt_colormap_apply(self.h, a, count, ta, nt, lo, hi, o),
                     "colormap_apply")
         return out
+
+    # ---- isosurfaces of tetrahedral meshes ----
+    def tet_isosurface(self, meshes, normals=True, capacity=None, count_only=False):
+        """spray_rt_tet_isosurface: the isosurfaces of tetrahedral meshes (see
+        _tet_table) in one batched call -> [(verts float32 [nv, 3], normals
+        float32 [nv, 3] or None (normals False, or a mesh without them), colors
+        int32 [nv] holding the 0x00RRGGBB bits, faces int32 [nf, 3] holding the
+        uint32 bits)] as GPU tensors of the exact sizes (a counting call
+        first).  capacity=(nverts, nfaces) skips the counting call and extracts
+        into buffers of that size per mesh (SPRAY_RT_ERR_LIMIT if one is too
+        small).  count_only: [(nverts, nfaces)] alone.  Enqueued on the
+        context's stream: sync() before reading the tensors on another stream."""
+        import torch
+        n = len(meshes)
+        arr, carr, keep = _tet_table(meshes)
+        m = max(n, 1)
+        nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        L = lib()
+        if capacity is None or count_only:
+            self._check(L.spray_rt_tet_isosurface(self.h, n, arr, carr, None, None, None, None,
+                                                  None, None, nv, nf), "tet_isosurface")
+            caps = [(nv[i], nf[i]) for i in range(n)]
+            if count_only:
+                return caps
+        else:
+            caps = [(int(capacity[0]), int(capacity[1]))] * n
+        dev = "cuda:%d" % self._device
+        # zeroed, one element at least: a buffer a failed call must not touch
+        v = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) for cv, _ in caps]
+        nr = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev)
+              if normals and meshes[i].get("normals") is not None else None
+              for i, (cv, _) in enumerate(caps)]
+        col = [torch.zeros(max(cv, 1), dtype=torch.int32, device=dev) for cv, _ in caps]
+        f = [torch.zeros((max(cf, 1), 3), dtype=torch.int32, device=dev) for _, cf in caps]
+
+        def ptrs(xs):
+            if all(x is None for x in xs):
+                return None
+            return (C.c_void_p * m)(*[None if x is None else x.data_ptr() for x in xs])
+
+        _fills_done()
+        try:
+            self._check(L.spray_rt_tet_isosurface(
+                self.h, n, arr, carr, ptrs(v), ptrs(nr), ptrs(col), ptrs(f),
+                (C.c_size_t * m)(*[c[0] for c in caps]), (C.c_size_t * m)(*[c[1] for c in caps]),
+                nv, nf), "tet_isosurface")
+        except SprayRtError as e:
+            e.counts = [(nv[i], nf[i]) for i in range(n)]
+            e.buffers = (v, [x for x in nr if x is not None], col, f)
+            raise
+        cut = lambda x, k: None if x is None else x[:k]
+        return [(v[i][:nv[i]], cut(nr[i], nv[i]), col[i][:nv[i]], f[i][:nf[i]])
+                for i in range(n)]
+
+    def tet_isosurface_domains(self, slots, meshes, normals=True, bounds=None):
+        """spray_rt_domains_tet_isosurface: the isosurfaces of tetrahedral meshes
+        (see _tet_table) into slots (empty or loaded), extracted and built on
+        the device; a slot carries normals where normals and its mesh has them,
+        colours where its mesh is mapped or has a colour.  bounds as in
+        refit_domains; slot_info(slot)["tris"] has the triangle counts."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(meshes) != n:
+            e = SprayRtError("tet_isosurface_domains: %d slots, %d meshes" % (n, len(meshes)))
+            e.code = -1
+            raise e
+        arr, carr, keep = _tet_table(meshes)
+        m = max(n, 1)
+        sl = (C.c_int * m)(*slots)
+        out = self._bounds_out(bounds, n)
+        b, k = _addr(out)
+        nf = (C.c_size_t * m)()
+        self._check(lib().spray_rt_domains_tet_isosurface(
+            self.h, n, sl, arr, carr, 1 if normals else 0, b, nf), "domains_tet_isosurface")
+        for s in slots:
+            self._nverts.pop(s, None)  # the vertex count is the extraction's
+        if bounds is True:
+            self.sync()
+            return out[:n].cpu().numpy()
+        return out
+
+    def tet_phase_times(self, on=None):
+        """spray_rt_tet_phase_times of the last tet extraction -> [ms to host
+        read 1, to host read 2, to the end of the enqueue, the sort's device
+        time]; on (True / False) first switches the sort's timing."""
+        if on is not None:
+            self._check(lib().spray_rt_tet_set_timing(self.h, 1 if on else 0), "tet_set_timing")
+        out = (C.c_double * 4)()
+        self._check(lib().spray_rt_tet_phase_times(self.h, out), "tet_phase_times")
+        return list(out)
 
     def slot_export(self, slot, what):
         """One array of a resident slot as numpy: SLOT_NODES / SLOT_QNODES4 as
