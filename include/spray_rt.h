@@ -520,6 +520,91 @@ int spray_rt_tet_phase_times(spray_rt_ctx_t ctx, double out_ms[4]);
 int spray_rt_tet_isosurface_host(const spray_rt_tetmesh* mesh, const spray_rt_grid_color* gcolor,
                                  size_t* nverts, size_t* nfaces, float* verts_out,
                                  float* vnormals_out, uint32_t* colors_out, uint32_t* faces_out);
+/* ---- isosurfaces of hexahedral, wedge, pyramid and tetrahedral cells ---- */
+/* Cell types and the order of points within a cell are VTK's. */
+#define SPRAY_RT_CELL_TET     10  /* 4 points */
+#define SPRAY_RT_CELL_HEX     12  /* 8: 0-1-2-3 one face in cyclic order, 4-5-6-7 the opposite
+                                     face, 4 above 0 */
+#define SPRAY_RT_CELL_WEDGE   13  /* 6: 0-1-2 a triangle, 3-4-5 the opposite one, 3 above 0 */
+#define SPRAY_RT_CELL_PYRAMID 14  /* 5: 0-1-2-3 the base in cyclic order, 4 the apex */
+/* One mixed unstructured mesh with a scalar per point and the isovalue to
+ * contour it at. */
+typedef struct spray_rt_cellmesh {
+  const float*    points;        /* [npoints][3]; device or host memory */
+  const uint8_t*  types;         /* [ncells] SPRAY_RT_CELL_* */
+  const uint32_t* offsets;       /* [ncells + 1]; cell i lists conn[offsets[i] .. offsets[i+1]) */
+  const uint32_t* conn;          /* [nconn] point indices */
+  const float*    values;        /* [npoints] */
+  const float*    point_normals; /* optional [npoints][3], as spray_rt_tetmesh */
+  size_t   npoints, ncells, nconn;
+  float    isovalue;
+  uint32_t color_rgb;
+  int32_t  has_color;
+} spray_rt_cellmesh;
+/* The surface is spray_rt_tet_isosurface's of a tet list that a fixed rule
+ * makes of the cells.  A tet cell is its four points as
+ * listed.  Any other cell is the cone from its apex over the faces that do
+ * not contain the apex.  With faces as local positions, quads in cyclic order,
+ *   hex      (0,1,2,3) (4,5,6,7) (0,1,5,4) (1,2,6,5) (2,3,7,6) (3,0,4,7)
+ *   wedge    (0,1,2) (3,4,5) (0,1,4,3) (1,2,5,4) (2,0,3,5)
+ *   pyramid  (0,1,2,3) (0,1,4) (1,2,4) (2,3,4) (3,0,4)
+ * the apex m is the local position of the cell's smallest point index (the
+ * lowest position on ties); each face in table order that does not contain m
+ * gives, as a triangle (q0,q1,q2), the tet (P[m], P[q0], P[q1], P[q2]), and as
+ * a quad, with j the position within the face of its smallest point index
+ * (lowest j on ties) and r_d = q[(j + d) mod 4], the tets (P[m], P[r0], P[r1],
+ * P[r2]) then (P[m], P[r0], P[r2], P[r3]): 6 tets per hex, 3 per wedge, 2 per
+ * pyramid, ordered by cell, then by face, then by the two triangles of a quad.
+ * Every quad face of the mesh is cut through its smallest point index from
+ * both sides, so the split is conforming whatever the cell types, and a hex
+ * mesh of a lattice numbered x fastest has the Kuhn split of
+ * spray_rt_isosurface.  A collapsed cell that lists a point twice goes
+ * through the same rule.
+ *
+ * spray_rt_cell_isosurface has the argument shapes and NULL conventions of
+ * spray_rt_tet_isosurface (gcolors fields are [npoints]).  Only the cells the
+ * surface crosses become tets on the device; the bytes are those of the full
+ * list.  At most three host reads per call: the cell pass's status and tet
+ * totals, then the tet extraction's two.
+ *
+ * SPRAY_RT_ERR_ARG, before anything is written and naming the mesh: a NULL
+ * pointer (ncells == 0 reads nothing and gives the empty surface), a
+ * non-finite isovalue, a bad colour map, vnormals[i] non-NULL for a mesh
+ * without point_normals, an unknown cell type, offsets[i+1] - offsets[i]
+ * different from the type's point count, offsets[i+1] > nconn, a point index
+ * >= npoints, or a non-finite value among what the call reads of a point some
+ * cell references, whether the surface crosses that cell or not (points no
+ * cell references are never read).  SPRAY_RT_ERR_LIMIT: ncells >= 2^29,
+ * nconn >= 2^32, npoints >= 2^32, 2^29 or more tets from crossing cells in
+ * one mesh, 2^32 or more crossing (tet, edge) instances in one call, more
+ * than 65,535 meshes. */
+int spray_rt_cell_isosurface(spray_rt_ctx_t ctx, int n, const spray_rt_cellmesh* meshes,
+                             const spray_rt_grid_color* gcolors, float* const* verts,
+                             float* const* vnormals, uint32_t* const* colors,
+                             uint32_t* const* faces, const size_t* cap_verts,
+                             const size_t* cap_faces, size_t* nverts_out, size_t* nfaces_out);
+/* Meshes in, resident slots out, as spray_rt_domains_tet_isosurface: slots[i]
+ * is byte for byte a slot of spray_rt_domains_build of the extracted mesh.  At
+ * most five host reads (the extraction's three and the build's two).  A failed
+ * call leaves every slot as it was; messages name the mesh and its slot.  Not
+ * for use while lanes run. */
+int spray_rt_domains_cell_isosurface(spray_rt_ctx_t ctx, int n, const int* slots,
+                                     const spray_rt_cellmesh* meshes,
+                                     const spray_rt_grid_color* gcolors, int with_normals,
+                                     float* d_bounds, size_t* nfaces_out);
+/* Where the last cell extraction of the context spent its time: out_ms[0]
+ * wall clock from entry to the cell pass's host read, out_ms[1..4] from there
+ * on as spray_rt_tet_phase_times' four. */
+int spray_rt_cell_phase_times(spray_rt_ctx_t ctx, double out_ms[5]);
+/* Host-only (no GPU; every array is host memory).  spray_rt_cell_split_host
+ * writes the full tet list of the rule, [*ntets][4] point indices (tets_out
+ * NULL: the count alone); it reads types, offsets and conn only.
+ * spray_rt_cell_isosurface_host is spray_rt_tet_isosurface_host of that list,
+ * and what the kernels write, byte for byte. */
+int spray_rt_cell_split_host(const spray_rt_cellmesh* mesh, size_t* ntets, uint32_t* tets_out);
+int spray_rt_cell_isosurface_host(const spray_rt_cellmesh* mesh, const spray_rt_grid_color* gcolor,
+                                  size_t* nverts, size_t* nfaces, float* verts_out,
+                                  float* vnormals_out, uint32_t* colors_out, uint32_t* faces_out);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes

@@ -68,6 +68,17 @@ class TetMesh(C.Structure):
 
 assert C.sizeof(TetMesh) == 64
 
+
+class CellMesh(C.Structure):
+    """spray_rt_cellmesh."""
+    _fields_ = [("points", C.c_void_p), ("types", C.c_void_p), ("offsets", C.c_void_p),
+                ("conn", C.c_void_p), ("values", C.c_void_p), ("point_normals", C.c_void_p),
+                ("npoints", C.c_size_t), ("ncells", C.c_size_t), ("nconn", C.c_size_t),
+                ("isovalue", C.c_float), ("color_rgb", C.c_uint32), ("has_color", C.c_int32)]
+
+
+assert C.sizeof(CellMesh) == 88
+
 # every symbol the public headers declare: (restype, argtypes)
 P = C.c_void_p
 SZ = C.c_size_t
@@ -105,6 +116,11 @@ SIGNATURES = {
     "spray_rt_tet_isosurface_host": (I, [P, P, P, P, P, P, P, P]),
     "spray_rt_tet_set_timing": (I, [P, I]),
     "spray_rt_tet_phase_times": (I, [P, P]),
+    "spray_rt_cell_isosurface": (I, [P, I, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_cell_isosurface": (I, [P, I, P, P, P, I, P, P]),
+    "spray_rt_cell_isosurface_host": (I, [P, P, P, P, P, P, P, P]),
+    "spray_rt_cell_split_host": (I, [P, P, P]),
+    "spray_rt_cell_phase_times": (I, [P, P]),
     "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
     "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),

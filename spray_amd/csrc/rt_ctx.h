@@ -101,6 +101,10 @@ struct spray_rt_ctx {
   bool tet_timing = false;
   double tet_ms[4] = {};
   hipEvent_t tet_ev[2] = {nullptr, nullptr};
+  spray_rt::detail::JobArena cell;  // job tables, records | staged mesh arrays, per-cell scratch
+  void* d_celltets = nullptr;       // cell isosurface: the tets of the crossing cells
+  size_t celltets_cap = 0;
+  double cell_ms = 0.0;  // spray_rt_cell_phase_times: wall clock to the cell pass's host read
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;

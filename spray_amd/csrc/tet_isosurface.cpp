@@ -26,6 +26,7 @@
 #include "spray_rt.h"
 #include "tet_common.h"
 #include "tet_kernels.h"
+#include "tet_pipeline.h"
 
 using namespace spray_rt;
 using namespace spray_rt::detail;
@@ -46,17 +47,6 @@ const char* mesh_error(const spray_rt_tetmesh& m, int* code) {
   if (uint64_t(m.ntets) >= kMaxTets) return "2^29 or more tets";
   if (uint64_t(m.npoints) >= kMaxPoints) return "2^32 or more points";
   *code = SPRAY_RT_OK;
-  return nullptr;
-}
-
-// ... with a mesh's colour map; a mesh without a colour field has none.
-const char* color_error(const spray_rt_grid_color* gc, float* scale) {
-  *scale = 0.0f;
-  if (!gc || !gc->field) return nullptr;
-  if (!gc->table_rgb) return "null colour table";
-  if (!cmap::map_scale(gc->ntable, gc->lo, gc->hi, scale))
-    return "the colour map is not a table of 1 to 4096 entries over lo < hi, both finite, with a "
-           "finite normal scale";
   return nullptr;
 }
 
@@ -82,7 +72,7 @@ int extract_host(const spray_rt_tetmesh& m, const spray_rt_grid_color* gc, bool 
   int code;
   if (mesh_error(m, &code)) return code;
   float cscale;
-  if (color_error(gc, &cscale)) return SPRAY_RT_ERR_ARG;
+  if (tet_color_error(gc, &cscale)) return SPRAY_RT_ERR_ARG;
   if (with_normals && !m.point_normals) return SPRAY_RT_ERR_ARG;
   const float* cf = gc ? gc->field : nullptr;
   const float* pn = with_normals ? m.point_normals : nullptr;
@@ -157,32 +147,33 @@ int extract_host(const spray_rt_tetmesh& m, const spray_rt_grid_color* gc, bool 
 
 // ---- the device extraction: count, read 1, weld, read 2, emit ----
 
-using Clock = std::chrono::steady_clock;
+using Clock = TetCall::Clock;
 double ms_since(Clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
 }
 
-struct TetCall {
-  HeadTake<TetJob> jobs;  // in the context's tet arena
-  HeadTake<uint32_t> status, offsets;
-  HeadTake<TetRec> recs;
-  HeadTake<TetInst> insts;
-  HeadTake<TetOut> outs;
-  size_t m_status = 0, m_rec = 0, m_insts = 0, m_outs = 0;  // the marks in front of them
-  uint32_t max_blocks = 0, max_iblocks = 0;
-  unsigned key_bits = 0;  // of the widest mesh's keys
-  bool staged = false;    // some array came from host memory
-  std::vector<TetRec> rec;
-  Clock::time_point t0 = Clock::now();  // the phase times of spray_rt_tet_phase_times
-};
-
-std::string mesh_name(int i, const int* slots) {
-  char buf[80];
+std::string mesh_name(const char* what, int i, const int* slots) {
+  char buf[96];
   if (slots)
-    snprintf(buf, sizeof(buf), "tet isosurface (mesh %d, slot %d)", i, slots[i]);
+    snprintf(buf, sizeof(buf), "%s (mesh %d, slot %d)", what, i, slots[i]);
   else
-    snprintf(buf, sizeof(buf), "tet isosurface (mesh %d)", i);
+    snprintf(buf, sizeof(buf), "%s (mesh %d)", what, i);
   return std::string(buf);
+}
+
+}  // namespace
+
+namespace spray_rt {
+namespace detail {
+
+const char* tet_color_error(const spray_rt_grid_color* gc, float* scale) {
+  *scale = 0.0f;
+  if (!gc || !gc->field) return nullptr;
+  if (!gc->table_rgb) return "null colour table";
+  if (!cmap::map_scale(gc->ntable, gc->lo, gc->hi, scale))
+    return "the colour map is not a table of 1 to 4096 entries over lo < hi, both finite, with a "
+           "finite normal scale";
+  return nullptr;
 }
 
 // Validates the meshes (and their colour maps, gcolors nullptr: none), runs the
@@ -194,19 +185,19 @@ int tet_count(spray_rt_ctx* c, int n, const spray_rt_tetmesh* meshes,
               const std::vector<char>& want_normals, TetCall* call) {
   const size_t nj = size_t(n);
   if (n > 65535)
-    return fail(c, SPRAY_RT_ERR_LIMIT, "tet isosurface: more than 65535 meshes in one call");
+    return fail(c, SPRAY_RT_ERR_LIMIT, "%s: more than 65535 meshes in one call", call->what);
   for (int i = 0; i < n; ++i) {
     int code;
     if (const char* why = mesh_error(meshes[i], &code))
-      return fail(c, code, "%s: %s", mesh_name(i, slots).c_str(), why);
+      return fail(c, code, "%s: %s", mesh_name(call->what, i, slots).c_str(), why);
     if (want_normals[size_t(i)] && !meshes[i].point_normals)
       return fail(c, SPRAY_RT_ERR_ARG, "%s: normals asked of a mesh without point_normals",
-                  mesh_name(i, slots).c_str());
+                  mesh_name(call->what, i, slots).c_str());
   }
   std::vector<float> cscale(nj, 0.0f);
   for (int i = 0; gcolors && i < n; ++i)
-    if (const char* why = color_error(&gcolors[i], &cscale[size_t(i)]))
-      return fail(c, SPRAY_RT_ERR_ARG, "%s: %s", mesh_name(i, slots).c_str(), why);
+    if (const char* why = tet_color_error(&gcolors[i], &cscale[size_t(i)]))
+      return fail(c, SPRAY_RT_ERR_ARG, "%s: %s", mesh_name(call->what, i, slots).c_str(), why);
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = stream_of(c);
 
@@ -307,12 +298,12 @@ int tet_count(spray_rt_ctx* c, int n, const spray_rt_tetmesh* meshes,
   uint64_t total = 0;
   for (int i = 0; i < n; ++i) {
     if (const char* why = status_error(h_status[i]))
-      return fail(c, SPRAY_RT_ERR_ARG, "%s: %s", mesh_name(i, slots).c_str(), why);
+      return fail(c, SPRAY_RT_ERR_ARG, "%s: %s", mesh_name(call->what, i, slots).c_str(), why);
     total += h_rec[i].ninst;
   }
   if (total >= kMaxInst)
-    return fail(c, SPRAY_RT_ERR_LIMIT,
-                "tet isosurface: 2^32 or more crossing-edge instances in one call");
+    return fail(c, SPRAY_RT_ERR_LIMIT, "%s: 2^32 or more crossing-edge instances in one call",
+                call->what);
   return SPRAY_RT_OK;
 }
 
@@ -396,6 +387,8 @@ int tet_weld(spray_rt_ctx* c, int n, TetCall* call) {
   return SPRAY_RT_OK;
 }
 
+namespace {
+
 // The vertex and face passes of a welded call into outs[n].
 int tet_emit(spray_rt_ctx* c, int n, const TetCall& call, const std::vector<TetOut>& outs) {
   hipStream_t s = stream_of(c);
@@ -413,6 +406,108 @@ int tet_emit(spray_rt_ctx* c, int n, const TetCall& call, const std::vector<TetO
 }
 
 }  // namespace
+
+int tet_to_buffers(spray_rt_ctx* c, int n, const TetCall& call, float* const* verts,
+                   float* const* vnormals, uint32_t* const* colors, uint32_t* const* faces,
+                   const size_t* cap_verts, const size_t* cap_faces, size_t* nverts_out,
+                   size_t* nfaces_out) {
+  for (int i = 0; i < n; ++i) {
+    if (nverts_out) nverts_out[i] = size_t(call.rec[size_t(i)].nverts);
+    if (nfaces_out) nfaces_out[i] = size_t(call.rec[size_t(i)].nfaces);
+  }
+  if (!verts && !vnormals && !colors && !faces) return SPRAY_RT_OK;
+  std::vector<TetOut> outs(size_t(n), TetOut{});
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    const TetRec& rec = call.rec[size_t(i)];
+    TetOut& O = outs[size_t(i)];
+    O.verts = verts ? verts[i] : nullptr;
+    O.normals = vnormals ? vnormals[i] : nullptr;
+    O.colors = colors ? colors[i] : nullptr;
+    O.faces = faces ? faces[i] : nullptr;
+    const bool per_vertex = O.verts || O.normals || O.colors;
+    if ((per_vertex && rec.nverts > cap_verts[i]) || (O.faces && rec.nfaces > cap_faces[i]))
+      return fail(c, SPRAY_RT_ERR_LIMIT,
+                  "%s (mesh %d): %llu vertices and %llu faces do not fit the buffers", call.what,
+                  i, static_cast<unsigned long long>(rec.nverts),
+                  static_cast<unsigned long long>(rec.nfaces));
+    O.cap_verts = per_vertex ? rec.nverts : 0;
+    O.cap_faces = O.faces ? rec.nfaces : 0;
+    any = any || per_vertex || O.faces;
+  }
+  if (!any) return SPRAY_RT_OK;
+  const int r = tet_emit(c, n, call, outs);
+  if (r) return r;
+  if (call.staged) HIPCHK(c, hipStreamSynchronize(stream_of(c)));  // host arrays: done on return
+  return SPRAY_RT_OK;
+}
+
+int tet_slots_error(spray_rt_ctx* c, const char* what, int n, const int* slots) {
+  for (int i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] > 1 << 20)
+      return fail(c, SPRAY_RT_ERR_ARG, "%s (mesh %d): bad slot %d", what, i, slots[i]);
+    for (int k = 0; k < i; ++k)
+      if (slots[k] == slots[i])
+        return fail(c, SPRAY_RT_ERR_ARG, "%s (mesh %d): slot %d listed twice", what, i, slots[i]);
+  }
+  return SPRAY_RT_OK;
+}
+
+int tet_to_slots(spray_rt_ctx* c, int n, const int* slots, const TetCall& call,
+                 const std::vector<char>& want_normals, const std::vector<char>& want_colors,
+                 float* d_bounds, size_t* nfaces_out) {
+  const size_t nj = size_t(n);
+  for (int i = 0; i < n; ++i)
+    if (call.rec[size_t(i)].nfaces >= kMaxTets)
+      return fail(c, SPRAY_RT_ERR_LIMIT, "%s: 2^29 or more faces",
+                  mesh_name(call.what, i, slots).c_str());
+
+  // ---- the meshes: context scratch, at the exact sizes ----
+  Layout M;  // of d_isomesh
+  std::vector<TetOut> outs(nj, TetOut{});
+  std::vector<Take<float>> t_verts(nj), t_normals(nj);
+  std::vector<Take<uint32_t>> t_colors(nj), t_faces(nj);
+  std::vector<size_t> nv(nj), nf(nj);
+  for (size_t k = 0; k < nj; ++k) {
+    outs[k].cap_verts = nv[k] = size_t(call.rec[k].nverts);
+    outs[k].cap_faces = nf[k] = size_t(call.rec[k].nfaces);
+    t_verts[k] = M.take<float>(3 * nv[k]);
+    if (want_normals[k]) t_normals[k] = M.take<float>(3 * nv[k]);
+    if (want_colors[k]) t_colors[k] = M.take<uint32_t>(nv[k]);
+    t_faces[k] = M.take<uint32_t>(3 * nf[k]);
+  }
+  int r = ensure(c, &c->d_isomesh, &c->isomesh_cap, std::max<size_t>(M.used, 256));
+  if (r) return r;
+  std::vector<const float*> pv(nj), pn(nj);
+  std::vector<const uint32_t*> pc(nj), pf(nj);
+  for (size_t k = 0; k < nj; ++k) {
+    TetOut& O = outs[k];
+    pv[k] = O.verts = t_verts[k].at(c->d_isomesh);
+    pn[k] = O.normals = t_normals[k] ? t_normals[k].at(c->d_isomesh) : nullptr;
+    pc[k] = O.colors = t_colors[k] ? t_colors[k].at(c->d_isomesh) : nullptr;
+    pf[k] = O.faces = t_faces[k].at(c->d_isomesh);
+  }
+  r = tet_emit(c, n, call, outs);
+  if (r) return r;
+
+  // ---- the slots: the device build on the extracted arrays ----
+  int job = -1;  // the build names the slot; name the mesh as well
+  r = domains_build(c, n, slots, pv.data(), nv.data(), pf.data(), nf.data(), pc.data(), pn.data(),
+                    d_bounds, &job);
+  if (r) {
+    const std::string msg = c->err;
+    if (job >= 0)
+      return fail(c, r, "%s (mesh %d, slot %d): %s", call.what, job, slots[job], msg.c_str());
+    return fail(c, r, "%s: %s", call.what, msg.c_str());
+  }
+  if (nfaces_out)
+    for (size_t k = 0; k < nj; ++k) nfaces_out[k] = nf[k];
+  if (call.staged) HIPCHK(c, hipStreamSynchronize(stream_of(c)));  // host arrays: done on return
+  return SPRAY_RT_OK;
+}
+
+}  // namespace detail
+}  // namespace spray_rt
 
 extern "C" {
 
@@ -462,35 +557,8 @@ int spray_rt_tet_isosurface(spray_rt_ctx_t c, int n, const spray_rt_tetmesh* mes
   if (r) return r;
   r = tet_weld(c, n, &call);
   if (r) return r;
-  for (int i = 0; i < n; ++i) {
-    if (nverts_out) nverts_out[i] = size_t(call.rec[size_t(i)].nverts);
-    if (nfaces_out) nfaces_out[i] = size_t(call.rec[size_t(i)].nfaces);
-  }
-  if (!verts && !vnormals && !colors && !faces) return SPRAY_RT_OK;
-  std::vector<TetOut> outs(size_t(n), TetOut{});
-  bool any = false;
-  for (int i = 0; i < n; ++i) {
-    const TetRec& rec = call.rec[size_t(i)];
-    TetOut& O = outs[size_t(i)];
-    O.verts = verts ? verts[i] : nullptr;
-    O.normals = vnormals ? vnormals[i] : nullptr;
-    O.colors = colors ? colors[i] : nullptr;
-    O.faces = faces ? faces[i] : nullptr;
-    const bool per_vertex = O.verts || O.normals || O.colors;
-    if ((per_vertex && rec.nverts > cap_verts[i]) || (O.faces && rec.nfaces > cap_faces[i]))
-      return fail(c, SPRAY_RT_ERR_LIMIT,
-                  "tet isosurface (mesh %d): %llu vertices and %llu faces do not fit the buffers",
-                  i, static_cast<unsigned long long>(rec.nverts),
-                  static_cast<unsigned long long>(rec.nfaces));
-    O.cap_verts = per_vertex ? rec.nverts : 0;
-    O.cap_faces = O.faces ? rec.nfaces : 0;
-    any = any || per_vertex || O.faces;
-  }
-  if (!any) return SPRAY_RT_OK;
-  r = tet_emit(c, n, call, outs);
-  if (r) return r;
-  if (call.staged) HIPCHK(c, hipStreamSynchronize(stream_of(c)));  // host arrays: done on return
-  return SPRAY_RT_OK;
+  return tet_to_buffers(c, n, call, verts, vnormals, colors, faces, cap_verts, cap_faces,
+                        nverts_out, nfaces_out);
 }
 
 int spray_rt_domains_tet_isosurface(spray_rt_ctx_t c, int n, const int* slots,
@@ -502,67 +570,18 @@ int spray_rt_domains_tet_isosurface(spray_rt_ctx_t c, int n, const int* slots,
     return fail(c, SPRAY_RT_ERR_ARG, "tet isosurface: null arguments");
   if (n == 0) return SPRAY_RT_OK;
   const size_t nj = size_t(n);
-  for (int i = 0; i < n; ++i) {
-    if (slots[i] < 0 || slots[i] > 1 << 20)
-      return fail(c, SPRAY_RT_ERR_ARG, "tet isosurface (mesh %d): bad slot %d", i, slots[i]);
-    for (int k = 0; k < i; ++k)
-      if (slots[k] == slots[i])
-        return fail(c, SPRAY_RT_ERR_ARG, "tet isosurface (mesh %d): slot %d listed twice", i,
-                    slots[i]);
+  if (const int r = tet_slots_error(c, "tet isosurface", n, slots)) return r;
+  std::vector<char> want_normals(nj, 0), want_colors(nj, 0);
+  for (size_t k = 0; k < nj; ++k) {
+    want_normals[k] = with_normals && meshes[k].point_normals;
+    want_colors[k] = meshes[k].has_color || (gcolors && gcolors[k].field);
   }
-  std::vector<char> want_normals(nj, 0);
-  for (size_t k = 0; k < nj; ++k) want_normals[k] = with_normals && meshes[k].point_normals;
   TetCall call;
   int r = tet_count(c, n, meshes, gcolors, slots, want_normals, &call);
   if (r) return r;
   r = tet_weld(c, n, &call);
   if (r) return r;
-  for (int i = 0; i < n; ++i)
-    if (call.rec[size_t(i)].nfaces >= kMaxTets)
-      return fail(c, SPRAY_RT_ERR_LIMIT, "%s: 2^29 or more faces", mesh_name(i, slots).c_str());
-
-  // ---- the meshes: context scratch, at the exact sizes ----
-  Layout M;  // of d_isomesh
-  std::vector<TetOut> outs(nj, TetOut{});
-  std::vector<Take<float>> t_verts(nj), t_normals(nj);
-  std::vector<Take<uint32_t>> t_colors(nj), t_faces(nj);
-  std::vector<size_t> nv(nj), nf(nj);
-  for (size_t k = 0; k < nj; ++k) {
-    outs[k].cap_verts = nv[k] = size_t(call.rec[k].nverts);
-    outs[k].cap_faces = nf[k] = size_t(call.rec[k].nfaces);
-    t_verts[k] = M.take<float>(3 * nv[k]);
-    if (want_normals[k]) t_normals[k] = M.take<float>(3 * nv[k]);
-    if (meshes[k].has_color || (gcolors && gcolors[k].field)) t_colors[k] = M.take<uint32_t>(nv[k]);
-    t_faces[k] = M.take<uint32_t>(3 * nf[k]);
-  }
-  r = ensure(c, &c->d_isomesh, &c->isomesh_cap, std::max<size_t>(M.used, 256));
-  if (r) return r;
-  std::vector<const float*> pv(nj), pn(nj);
-  std::vector<const uint32_t*> pc(nj), pf(nj);
-  for (size_t k = 0; k < nj; ++k) {
-    TetOut& O = outs[k];
-    pv[k] = O.verts = t_verts[k].at(c->d_isomesh);
-    pn[k] = O.normals = t_normals[k] ? t_normals[k].at(c->d_isomesh) : nullptr;
-    pc[k] = O.colors = t_colors[k] ? t_colors[k].at(c->d_isomesh) : nullptr;
-    pf[k] = O.faces = t_faces[k].at(c->d_isomesh);
-  }
-  r = tet_emit(c, n, call, outs);
-  if (r) return r;
-
-  // ---- the slots: the device build on the extracted arrays ----
-  int job = -1;  // the build names the slot; name the mesh as well
-  r = domains_build(c, n, slots, pv.data(), nv.data(), pf.data(), nf.data(), pc.data(), pn.data(),
-                    d_bounds, &job);
-  if (r) {
-    const std::string msg = c->err;
-    if (job >= 0)
-      return fail(c, r, "tet isosurface (mesh %d, slot %d): %s", job, slots[job], msg.c_str());
-    return fail(c, r, "tet isosurface: %s", msg.c_str());
-  }
-  if (nfaces_out)
-    for (size_t k = 0; k < nj; ++k) nfaces_out[k] = nf[k];
-  if (call.staged) HIPCHK(c, hipStreamSynchronize(stream_of(c)));  // host arrays: done on return
-  return SPRAY_RT_OK;
+  return tet_to_slots(c, n, slots, call, want_normals, want_colors, d_bounds, nfaces_out);
 }
 
 }  // extern "C"

@@ -13,11 +13,12 @@ import ctypes as C
 import numpy as np
 
 from ._native import (HIT_DTYPE, INVALID_ID, RAY_DTYPE, RTC_ISECT_DTYPE, BsdfRec,
-                      SprayRtError, TetMesh, lib)
+                      SprayRtError, CellMesh, TetMesh, lib)
 
 __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_rays",
            "bvh_refit_host", "bvh_build_device_host", "isosurface_host",
-           "isosurface_mapped_host", "colormap_host", "tet_isosurface_host", "SLOT_COLORS",
+           "isosurface_mapped_host", "colormap_host", "tet_isosurface_host",
+           "cell_isosurface_host", "cell_split_host", "SLOT_COLORS",
            "SLOT_FACES",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
@@ -379,6 +380,125 @@ def tet_isosurface_host(points, tets, values, iso, normals=None, cfield=None, cm
             e = SprayRtError("tet_isosurface_host failed (%d)" % rc)
             e.code = rc
             raise e
+
+    call(None, None, None, None)
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals is not None else None
+    c = np.zeros(nv.value, np.uint32)
+    f = np.zeros((nf.value, 3), np.uint32)
+    call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, f.ctypes.data)
+    return v, n, c, f
+
+
+def _cell_list(x, dtype, what):
+    """x as the flat array of dtype (uint8 or uint32; int32 bits pass as uint32)
+    the engine reads: numpy or a torch tensor on the GPU -> (array, count)."""
+    size = np.dtype(dtype).itemsize
+    if hasattr(x, "data_ptr"):
+        if x.element_size() != size or x.is_floating_point():
+            raise TypeError("cell_isosurface: %s are %s" % (what, np.dtype(dtype).name))
+        return x, x.numel()
+    x = np.asarray(x)
+    if x.dtype.kind == "i" and x.dtype.itemsize == size:
+        x = x.view(dtype)
+    x = np.ascontiguousarray(x, dtype)
+    return x, x.size
+
+
+def _cell_table(meshes):
+    """Dicts with "points" (float32 [np, 3]), "types" (uint8 [nc], the
+    SPRAY_RT_CELL_* = VTK codes), "offsets" (uint32 [nc + 1]), "conn" (uint32
+    [nconn]), "values" (float32 [np]), "iso" and optionally "normals", "color",
+    "cfield" with "cmap" as in _tet_table -> (spray_rt_cellmesh array,
+    spray_rt_grid_color array, keepalive).  Arrays are numpy arrays or torch
+    tensors on the GPU."""
+    arr = (CellMesh * max(len(meshes), 1))()
+    carr = (_GridColor * max(len(meshes), 1))()
+    keep = []
+
+    def put(x):
+        a, k = _addr(x)
+        keep.append(k)
+        return a
+
+    for m, rec, crec in zip(meshes, arr, carr):
+        points, npts = _tet_array(m["points"], np.float32, 3, "points")
+        values, nval = _tet_array(m["values"], np.float32, 0, "values")
+        if nval != npts:
+            raise ValueError("cell_isosurface: one value per point")
+        types, ncells = _cell_list(m["types"], np.uint8, "types")
+        offsets, noff = _cell_list(m["offsets"], np.uint32, "offsets")
+        conn, nconn = _cell_list(m["conn"], np.uint32, "conn")
+        if noff != ncells + 1:
+            raise ValueError("cell_isosurface: one offset per cell and one more")
+        rec.points, rec.values = put(points), put(values)
+        rec.types, rec.offsets, rec.conn = put(types), put(offsets), put(conn)
+        rec.npoints, rec.ncells, rec.nconn = npts, ncells, nconn
+        if m.get("normals") is not None:
+            nrm, nn = _tet_array(m["normals"], np.float32, 3, "normals")
+            if nn != npts:
+                raise ValueError("cell_isosurface: one normal per point")
+            rec.point_normals = put(nrm)
+        rec.isovalue = float(m["iso"])
+        color = m.get("color")
+        rec.has_color = 0 if color is None else 1
+        rec.color_rgb = 0 if color is None else int(color)
+        if m.get("cfield") is not None:
+            cf, nc = _tet_array(m["cfield"], np.float32, 0, "colour samples")
+            if nc != npts:
+                raise ValueError("cell_isosurface: one colour sample per point")
+            crec.field = put(cf)
+            if m.get("cmap") is not None:
+                t, crec.table_rgb, crec.ntable, crec.lo, crec.hi = _cmap_args(m["cmap"])
+                keep.append(t)
+    return arr, carr, keep
+
+
+def _cell_fail(what, rc):
+    e = SprayRtError("%s failed (%d)" % (what, rc))
+    e.code = rc
+    raise e
+
+
+def cell_split_host(types, offsets, conn, npoints):
+    """spray_rt_cell_split_host (no GPU): the full tet list of the split rule
+     of a mesh's cells -> uint32 [ntets, 4]."""
+    types, ncells = _cell_list(types, np.uint8, "types")
+    offsets, noff = _cell_list(offsets, np.uint32, "offsets")
+    conn, nconn = _cell_list(conn, np.uint32, "conn")
+    if noff != ncells + 1:
+        raise ValueError("cell_split_host: one offset per cell and one more")
+    rec = CellMesh()
+    rec.types, rec.offsets, rec.conn = types.ctypes.data, offsets.ctypes.data, conn.ctypes.data
+    rec.npoints, rec.ncells, rec.nconn = int(npoints), ncells, nconn
+    L = lib()
+    nt = C.c_size_t()
+    rc = L.spray_rt_cell_split_host(C.byref(rec), C.byref(nt), None)
+    if rc != 0:
+        _cell_fail("cell_split_host", rc)
+    tets = np.zeros((nt.value, 4), np.uint32)
+    rc = L.spray_rt_cell_split_host(C.byref(rec), C.byref(nt), tets.ctypes.data)
+    if rc != 0:
+        _cell_fail("cell_split_host", rc)
+    return tets
+
+
+def cell_isosurface_host(points, types, offsets, conn, values, iso, normals=None, cfield=None,
+                         cmap=None, color=None):
+    """spray_rt_cell_isosurface_host (no GPU): the mesh RtContext.cell_isosurface
+    extracts from a mesh of mixed cells (see _cell_table; numpy arrays), with
+    tet_isosurface_host's results."""
+    m = dict(points=points, types=types, offsets=offsets, conn=conn, values=values, iso=iso,
+             normals=normals, cfield=cfield, cmap=cmap, color=color)
+    arr, carr, keep = _cell_table([m])
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_cell_isosurface_host(C.addressof(arr), C.addressof(carr), C.byref(nv),
+                                             C.byref(nf), *outs)
+        if rc != 0:
+            _cell_fail("cell_isosurface_host", rc)
 
     call(None, None, None, None)
     v = np.zeros((nv.value, 3), np.float32)
@@ -852,15 +972,20 @@ class RtContext:
         into buffers of that size per mesh (SPRAY_RT_ERR_LIMIT if one is too
         small).  count_only: [(nverts, nfaces)] alone.  Enqueued on the
         context's stream: sync() before reading the tensors on another stream."""
+        return self._mesh_isosurface(lib().spray_rt_tet_isosurface, "tet_isosurface",
+                                     _tet_table(meshes), meshes, normals, capacity, count_only)
+
+    def _mesh_isosurface(self, fn, what, table, meshes, normals, capacity, count_only):
+        """The body of tet_isosurface / cell_isosurface: fn the C entry point,
+        table the (mesh array, colour array, keepalive) of meshes."""
         import torch
         n = len(meshes)
-        arr, carr, keep = _tet_table(meshes)
+        arr, carr, keep = table
         m = max(n, 1)
         nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
-        L = lib()
         if capacity is None or count_only:
-            self._check(L.spray_rt_tet_isosurface(self.h, n, arr, carr, None, None, None, None,
-                                                  None, None, nv, nf), "tet_isosurface")
+            self._check(fn(self.h, n, arr, carr, None, None, None, None, None, None, nv, nf),
+                        what)
             caps = [(nv[i], nf[i]) for i in range(n)]
             if count_only:
                 return caps
@@ -882,10 +1007,10 @@ class RtContext:
 
         _fills_done()
         try:
-            self._check(L.spray_rt_tet_isosurface(
+            self._check(fn(
                 self.h, n, arr, carr, ptrs(v), ptrs(nr), ptrs(col), ptrs(f),
                 (C.c_size_t * m)(*[c[0] for c in caps]), (C.c_size_t * m)(*[c[1] for c in caps]),
-                nv, nf), "tet_isosurface")
+                nv, nf), what)
         except SprayRtError as e:
             e.counts = [(nv[i], nf[i]) for i in range(n)]
             e.buffers = (v, [x for x in nr if x is not None], col, f)
@@ -900,20 +1025,25 @@ class RtContext:
         the device; a slot carries normals where normals and its mesh has them,
         colours where its mesh is mapped or has a colour.  bounds as in
         refit_domains; slot_info(slot)["tris"] has the triangle counts."""
+        return self._mesh_isosurface_domains(lib().spray_rt_domains_tet_isosurface,
+                                             "tet_isosurface_domains", "domains_tet_isosurface",
+                                             _tet_table, slots, meshes, normals, bounds)
+
+    def _mesh_isosurface_domains(self, fn, name, what, table_of, slots, meshes, normals, bounds):
+        """The body of tet_isosurface_domains / cell_isosurface_domains."""
         slots = [int(s) for s in slots]
         n = len(slots)
         if len(meshes) != n:
-            e = SprayRtError("tet_isosurface_domains: %d slots, %d meshes" % (n, len(meshes)))
+            e = SprayRtError("%s: %d slots, %d meshes" % (name, n, len(meshes)))
             e.code = -1
             raise e
-        arr, carr, keep = _tet_table(meshes)
+        arr, carr, keep = table_of(meshes)
         m = max(n, 1)
         sl = (C.c_int * m)(*slots)
         out = self._bounds_out(bounds, n)
         b, k = _addr(out)
         nf = (C.c_size_t * m)()
-        self._check(lib().spray_rt_domains_tet_isosurface(
-            self.h, n, sl, arr, carr, 1 if normals else 0, b, nf), "domains_tet_isosurface")
+        self._check(fn(self.h, n, sl, arr, carr, 1 if normals else 0, b, nf), what)
         for s in slots:
             self._nverts.pop(s, None)  # the vertex count is the extraction's
         if bounds is True:
@@ -929,6 +1059,27 @@ class RtContext:
             self._check(lib().spray_rt_tet_set_timing(self.h, 1 if on else 0), "tet_set_timing")
         out = (C.c_double * 4)()
         self._check(lib().spray_rt_tet_phase_times(self.h, out), "tet_phase_times")
+        return list(out)
+
+    # ---- isosurfaces of hexahedral, wedge, pyramid and tet cells ----
+    def cell_isosurface(self, meshes, normals=True, capacity=None, count_only=False):
+        """spray_rt_cell_isosurface: tet_isosurface for meshes of mixed cells
+        (see _cell_table), with its arguments and results."""
+        return self._mesh_isosurface(lib().spray_rt_cell_isosurface, "cell_isosurface",
+                                     _cell_table(meshes), meshes, normals, capacity, count_only)
+
+    def cell_isosurface_domains(self, slots, meshes, normals=True, bounds=None):
+        """spray_rt_domains_cell_isosurface: tet_isosurface_domains for meshes of
+        mixed cells (see _cell_table)."""
+        return self._mesh_isosurface_domains(lib().spray_rt_domains_cell_isosurface,
+                                             "cell_isosurface_domains", "domains_cell_isosurface",
+                                             _cell_table, slots, meshes, normals, bounds)
+
+    def cell_phase_times(self):
+        """spray_rt_cell_phase_times of the last cell extraction -> [ms to the
+        cell pass's host read, then tet_phase_times' four from there on]."""
+        out = (C.c_double * 5)()
+        self._check(lib().spray_rt_cell_phase_times(self.h, out), "cell_phase_times")
         return list(out)
 
     def slot_export(self, slot, what):
