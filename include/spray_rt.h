@@ -1091,7 +1091,11 @@ int spray_rt_insitu_partition(const float* boxes, int ndomains, const float scen
 int spray_rt_insitu_partition_mode(const float* boxes, int ndomains, const float scene_bound[6],
                                    int nranks, int mode, int* owner_out);
 /* This rank's part of a frame: rays[n] / pixid / samid are its eye rays
- * (spray_rt_eye_rays_insitu of its stripe; samid = blocking-tile sample id),
+ * (spray_rt_eye_rays_insitu of its stripe; samid = blocking-tile sample id;
+ * tnear SPRAY_RAY_EPSILON and tfar +inf, as every radiance ray of the
+ * reference: the exchange does not send the two and the receiver sets them
+ * to these values, while the all-local frame of world 1 walks the records as
+ * they are, so other extents give results that depend on the route),
  * traced for shader->bounces bounces across the group; the contributions
  * of the samples this rank shades are added to image_rgba (device float
  * [w*h*4], scaled 1/spp).  totals (host, optional): the group's radiance

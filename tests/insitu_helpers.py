@@ -33,12 +33,26 @@ class OracleLocal:
     """Per-rank local work on the CPU oracle: a scene holding only this
     rank's meshes and every domain box."""
 
-    def __init__(self, po, owner, rank, desc=WAVELETS64, ply=SCENES):
+    def __init__(self, po, owner, rank, desc=WAVELETS64, ply=SCENES, meshes=None):
+        """meshes: (meshes, boxes, colors, normals) of a scene held in memory
+        (ray_cases.variant) instead of a scene file -- the rank's own domains
+        with their meshes, the others as boxes, as load_scene(only=...)."""
         mine = {d for d in range(len(owner)) if owner[d] == rank}
         self.po = po
-        self.sc, self.domains, _ = po.load_scene(desc, ply, only=mine)
-        self.boxes = np.array([d["world_bound"] for d in self.domains], np.float32)
         self.owner = np.asarray(owner)
+        if meshes is None:
+            self.sc, self.domains, _ = po.load_scene(desc, ply, only=mine)
+            self.boxes = np.array([d["world_bound"] for d in self.domains], np.float32)
+            return
+        ms, boxes, colors, normals = meshes
+        self.domains = None
+        self.boxes = np.ascontiguousarray(boxes, np.float32)
+        self.sc = po.Scene(len(ms))
+        for i, (v, f) in enumerate(ms):
+            if i in mine:
+                self.sc.set_domain(i, v, f, colors[i], normals[i], self.boxes[i])
+            else:
+                self.sc.set_box(i, self.boxes[i])
 
     def _od(self, rays):
         r = rays.numpy()
@@ -57,9 +71,17 @@ class OracleLocal:
                 m[i] |= 1 << int(self.owner[ids[i, k]])
         return torch.from_numpy(m)
 
-    def intersect_keyed(self, rays):
+    def intersect_keyed(self, rays, extents=False):
+        """extents: the hit within the record's own (tnear, tfar] (columns 3
+        and 7); the list position comes from the domain query, which ignores
+        them.  Default: the radiance rays' 0.001 / +inf."""
         o, d = self._od(rays)
-        hits, _ = self.sc.intersect(o, d)
+        if extents:
+            r = rays.numpy()
+            hits, _ = self.sc.intersect(o, d, tnear=np.ascontiguousarray(r[:, 3]),
+                                        tfar=np.ascontiguousarray(r[:, 7]))
+        else:
+            hits, _ = self.sc.intersect(o, d)
         ids, cnt = self._lists(rays)
         keys = np.full(len(hits), MISS_KEY, np.int64)
         h = hits["domain"] >= 0
@@ -114,6 +136,14 @@ def reference_frame(po, sh, bsdfs, cam, img_w, img_h, spp, block, desc=WAVELETS6
     (radiance rays, shadow rays))."""
     org, d, pix, sam = po.eye_rays_insitu(cam, img_w, spp, block, block)
     sc, _, _ = po.load_scene(desc, ply)
+    return reference_frame_rays(po, sh, bsdfs, sc, org, d, pix, sam, img_w, img_h, spp)
+
+
+def reference_frame_rays(po, sh, bsdfs, sc, org, d, pix, sam, img_w, img_h, spp):
+    """reference_frame's core on given eye rays (org / d are the callers' and
+    stay unchanged) and a whole-scene oracle `sc`."""
+    org, d = np.array(org, np.float32, order="C"), np.array(d, np.float32, order="C")
+    pix, sam = np.ascontiguousarray(pix, np.int32), np.ascontiguousarray(sam, np.int32)
     n = len(org)
     ns = po.shadow_slots(sh)
     w = np.ones((n, 3), np.float32)

@@ -1,7 +1,12 @@
 """A small multi-domain scene, the hard ray classes and a float64 reference
-for the scene-path tests (test_ray_cases.py, test_gpu_ray_cases.py).  Pure
-numpy; whatever needs the oracle (the `extents` and `nonfinite` classes start
-from hitting rays) takes the oracle's scene as an argument.
+for the scene-path tests (test_ray_cases.py, test_gpu_ray_cases.py), and the
+same classes as the eye rays of in-situ frames with their partitions,
+shading set-up and whole-scene reference frame (test_insitu_ray_cases.py,
+test_gpu_insitu_ray_cases.py).  The scene, the classes and the float64
+reference are pure numpy; whatever needs the oracle (the `extents` and
+`nonfinite` classes start from hitting rays) takes the oracle's scene as an
+argument, and the in-situ helpers (frame_reference, cross_rank_ties) import
+insitu_helpers, and with it torch, when they are called.
 
 Scene: eight touching domains in a 2 x 2 x 2 arrangement of 4-unit cells plus
 one curved domain.  A lattice domain is the welded surface of three cubes
@@ -29,6 +34,12 @@ NDOM = 9
 LARGE = 1.0e4  # the large-coordinate variant's translation (every axis)
 CLASSES = ("axis_off", "axis_lattice", "tiny", "edge", "surface", "extents", "random")
 TNEAR, TFAR = F32(0.001), F32(np.inf)
+# the in-situ partitions of the scene over two ranks (test_insitu_ray_cases.py):
+# domain 4i + 2j + k on rank (i + j + k) % 2 and the curved domain on rank 0,
+# so every x pair and z pair that shares coincident triangles is split; and
+# every domain on rank 1 (rank 0 holds rays only)
+OWNER_CHECKER = tuple((i + j + k) % 2 for i in (0, 1) for j in (0, 1) for k in (0, 1)) + (0,)
+OWNER_ONE = (1,) * NDOM
 
 
 # --------------------------------------------------------------------------
@@ -463,6 +474,82 @@ def oracle_results(var, name):
         o, oc = var["osc"].occluded(c["org"], c["dir"], tnear=c["tnear"], tfar=c["tfar"])
         var["ref"][name] = (h, o, hc, oc)
     return var["ref"][name]
+
+
+def frame_inputs(var, name, spp=2):
+    """Class `name` as the eye rays of an in-situ frame: dict(org, dir, pix,
+    sam, w, h, spp) with pixid = i // spp (a pixel's samples adjacent, the
+    in-situ order), samid = i, and the smallest near-square image that holds
+    ceil(n / spp) pixels.  The in-situ forms take radiance rays with the
+    default extents (tnear 0.001, tfar +inf), so the class's own tnear / tfar
+    are not part of the frame."""
+    c = var["classes"][name]
+    n = len(c["org"])
+    npix = -(-n // spp)
+    w = int(np.ceil(np.sqrt(npix)))
+    h = -(-npix // w)
+    i = np.arange(n, dtype=np.int32)
+    return dict(org=c["org"], dir=c["dir"], pix=(i // spp).astype(np.int32), sam=i, w=w, h=h,
+                spp=spp)
+
+
+# the shading set-up of the in-situ frames on this scene, the same on the
+# oracle's and the engine's side: one point light that moves with the scene,
+# every domain diffuse, ks 0.4, shininess 10
+SHADING = {"pt1": ("pt", 1, 1), "pt3": ("pt", 3, 2), "ao4": ("ao", 1, 4)}  # kind, bounces, samples
+BSDFS = ((0, 0.8, 0.7, 0.6),) * NDOM
+KS, SHININESS = (0.4, 0.4, 0.4), 10.0
+
+
+def frame_lights(offset):
+    off = float(offset)
+    return [(0, 4.0 + off, 30.0 + off, 60.0 + off, 1.0, 1.0, 1.0)]
+
+
+def frame_shader(make, offset, case):
+    """make: pyoracle.shader or spray_amd.frame.make_shader."""
+    kind, bounces, samples = SHADING[case]
+    return make(kind, bounces, samples, KS, SHININESS, frame_lights(offset))
+
+
+def frame_reference(oracle, var, offset, name, case, inputs=None):
+    """(records, image, totals) of the whole-scene reference frame
+    (insitu_helpers.reference_frame_rays) on frame_inputs(var, name), or on
+    `inputs` (then `name` is only a label); computed once per set of eye
+    rays and shading case."""
+    import hashlib
+    import insitu_helpers as H
+    fi = frame_inputs(var, name) if inputs is None else inputs
+    rays = hashlib.sha1(np.ascontiguousarray(fi["org"]).tobytes() +
+                        np.ascontiguousarray(fi["dir"]).tobytes()).hexdigest()
+    key = ("frame", name, case, rays, fi["w"], fi["h"], fi["spp"])
+    if key not in var["ref"]:
+        sh = frame_shader(oracle.shader, offset, case)
+        var["ref"][key] = H.reference_frame_rays(oracle, sh, list(BSDFS), var["osc"], fi["org"],
+                                                 fi["dir"], fi["pix"], fi["sam"], fi["w"],
+                                                 fi["h"], fi["spp"])
+    return var["ref"][key]
+
+
+def bounce_counts(ref, bounce):
+    """(hits, shadow rays, occluded shadow rays) of one bounce of a frame's
+    reference records."""
+    rows = [v for (b, _), v in ref.items() if b == bounce]
+    return (len(rows), sum(bin(v[1]).count("1") for v in rows),
+            sum(bin(v[2]).count("1") for v in rows))
+
+
+def cross_rank_ties(oracle, var, owner, org, d):
+    """Indices of the rays on which both ranks of the two-rank partition
+    `owner` hit at the same t bits (the winning ones: the list position
+    decides), from the oracle alone."""
+    import insitu_helpers as H
+    meshes = (var["meshes"], var["boxes"], var["colors"], var["normals"])
+    rays = H.rays_tensor(org, d)
+    keys = [H.OracleLocal(oracle, owner, r, meshes=meshes).intersect_keyed(rays)[1].numpy()
+            for r in (0, 1)]
+    both = (keys[0] != H.MISS_KEY) & (keys[1] != H.MISS_KEY)
+    return np.flatnonzero(both & ((keys[0] >> 32) == (keys[1] >> 32)))
 
 
 def check_against_f64(var, name, hit, t=None):

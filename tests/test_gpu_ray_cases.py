@@ -299,7 +299,212 @@ def form_ooc(e, name, slots):
         oc.close()
 
 
+def between(share, what):
+    assert 0 < share < 1, (what, share)
+
+
+def form_occluded_order(e, name):
+    """occluded_scene_order: the identity (order = NULL), a seeded
+    permutation, and a device count below the buffer length (the entries
+    beyond it untouched), per lane and adaptive."""
+    c = e.var["classes"][name]
+    _, ref, _, _ = RC.oracle_results(e.var, name)
+    n = len(ref)
+    T = e.torch
+    between(ref.mean(), (name, "occluded share"))
+    rays = dev_rays(e, c)
+    perm = np.random.default_rng(23).permutation(n).astype(np.int32)
+    k = 2 * n // 3 + 1  # no multiple of the wave
+    try:
+        for mode in (e.rt.RAYS_ADAPTIVE, e.rt.RAYS_INCOHERENT):
+            e.rt.set_coherence(mode)
+            for order in (None, perm):
+                for count in (n, k):
+                    occ = T.full((n,), 9, dtype=T.uint8, device="cuda")
+                    cnt = T.full((1,), count, dtype=T.int32, device="cuda")
+                    e.rt.occluded_scene_order(rays, n, None if order is None else dev_i32(e, order),
+                                              cnt, occ)
+                    e.rt.sync()
+                    o = occ.cpu().numpy()
+                    done = np.zeros(n, bool)
+                    done[np.arange(count) if order is None else order[:count]] = True
+                    what = (name, mode, order is not None, count, "occluded_scene_order")
+                    same_occ(o[done], ref[done], what)
+                    assert (o[~done] == 9).all(), what
+    finally:
+        e.rt.set_coherence(e.rt.RAYS_ADAPTIVE)
+
+
+def dev_i32(e, a):
+    return e.torch.from_numpy(np.ascontiguousarray(a, np.int32)).cuda()
+
+
+def form_occluded_devcount(e, name):
+    c = e.var["classes"][name]
+    _, ref, _, _ = RC.oracle_results(e.var, name)
+    n = len(ref)
+    T = e.torch
+    rays = dev_rays(e, c)
+    for count in (0, 1, 65, n):
+        occ = T.full((n,), 9, dtype=T.uint8, device="cuda")
+        cnt = T.full((1,), count, dtype=T.int32, device="cuda")
+        e.rt.occluded_scene_devcount(rays, n, cnt, occ)
+        e.rt.sync()
+        o = occ.cpu().numpy()
+        same_occ(o[:count], ref[:count], (name, count, "occluded_scene_devcount"))
+        assert (o[count:] == 9).all(), (name, count)
+
+
+def scene_shade(e):
+    shade = SHADE.copy()
+    shade[:3] += np.float32(e.var["boxes"][0, 0])  # the light moves with the scene
+    return shade
+
+
+def form_spawn_pt(e, name):
+    """spawn_shadows_pt on the oracle's hits of the class against the
+    oracle's spawn (count, sources, rays bit for bit); the spawned rays'
+    any hit against the oracle's."""
+    c = e.var["classes"][name]
+    hits, _, _, _ = RC.oracle_results(e.var, name)
+    n = len(hits)
+    T = e.torch
+    shade = scene_shade(e)
+    so, sd, src = e.oracle.spawn_shadows_pt(c["org"], c["dir"], hits, shade[0:3], shade[3:6],
+                                            shade[6:9], shade[9])
+    srays = T.zeros(n * 32, dtype=T.uint8, device="cuda")
+    osrc = T.full((n,), -1, dtype=T.int32, device="cuda")
+    cnt = T.full((1,), 123, dtype=T.int32, device="cuda")
+    e.rt.spawn_shadows_pt(dev_rays(e, c), dev(e, hits), n, shade, srays, osrc, cnt)
+    e.rt.sync()
+    m = int(cnt.item())
+    assert m == len(so) and 0 < m < n, (name, m, len(so))
+    assert np.array_equal(osrc[:m].cpu().numpy(), src), name
+    sr = srays[: m * 32].cpu().numpy().view(e.spray.RAY_DTYPE)
+    assert np.array_equal(sr["org"].view(np.uint32), so.view(np.uint32)), name
+    assert np.array_equal(sr["dir"].view(np.uint32), sd.view(np.uint32)), name
+    assert (sr["tnear"] == RC.TNEAR).all() and np.isinf(sr["tfar"]).all()
+    ref, _ = e.var["osc"].occluded(so, sd)
+    between(ref.mean(), (name, "occluded shadow rays"))
+    occ = T.full((m,), 9, dtype=T.uint8, device="cuda")
+    e.rt.occluded_scene(srays[: m * 32], occ)
+    e.rt.sync()
+    same_occ(occ.cpu().numpy(), ref, (name, "occluded_scene of spawn_shadows_pt"))
+
+
+def form_ao(e, name, ns):
+    """The AO chain on the oracle's hits of the class, two rays per pixel:
+    spawn_shadows_ao against the oracle's spawn; _ordered and _traced as
+    permutations of it; occluded_scene_order on both; the pairs form
+    (spawn_shadows_ao_pairs + occluded_ao_pairs, and occluded_ao) with the
+    traced spawn's (source, sample) pairs and the written rays' occlusion."""
+    c = e.var["classes"][name]
+    hits, _, _, _ = RC.oracle_results(e.var, name)
+    n = len(hits)
+    T = e.torch
+    pix = (np.arange(n) // 2).astype(np.int32)
+    npix = int(pix[-1]) + 1
+    so, sd, src = e.oracle.spawn_shadows_ao(c["org"], c["dir"], pix, hits, ns)
+    m = len(so)
+    assert m > ns * n // 4, (name, m)
+    ref, _ = e.var["osc"].occluded(so, sd)
+    between(ref.mean(), (name, ns, "occluded AO rays"))
+    rays, h, pixid = dev_rays(e, c), dev(e, hits), dev_i32(e, pix)
+    what = (name, ns)
+
+    def spawn(**kw):
+        out = T.zeros((n * ns, 8), dtype=T.float32, device="cuda")
+        osrc = T.full((n * ns,), -1, dtype=T.int32, device="cuda")
+        cnt = T.full((1,), 123, dtype=T.int32, device="cuda")
+        e.rt.spawn_shadows_ao(rays, h, pixid, n, ns, out, osrc, cnt, **kw)
+        e.rt.sync()
+        assert int(cnt.item()) == m, (what, kw.keys(), int(cnt.item()), m)
+        return out, osrc[:m].cpu().numpy(), cnt
+
+    def any_hit(out, order, cnt):
+        occ = T.full((n * ns,), 9, dtype=T.uint8, device="cuda")
+        e.rt.occluded_scene_order(out, n * ns, order, cnt, occ)
+        e.rt.sync()
+        o = occ.cpu().numpy()
+        assert (o[m:] == 9).all(), what
+        return o[:m]
+
+    out, osrc, cnt = spawn()
+    g = out[:m].cpu().numpy()
+    assert np.array_equal(osrc, src), what
+    assert g[:, 0:3].tobytes() == np.ascontiguousarray(so).tobytes(), what
+    assert g[:, 4:7].tobytes() == np.ascontiguousarray(sd).tobytes(), what
+    assert (g[:, 3] == RC.TNEAR).all() and np.isinf(g[:, 7]).all(), what
+    try:
+        e.rt.set_coherence(e.rt.RAYS_INCOHERENT)
+        same_occ(any_hit(out, None, cnt), ref, (what, "identity"))
+        # ordered: the same rays and a permutation of [0, m) as trace order
+        order = T.full((n * ns,), -1, dtype=T.int32, device="cuda")
+        out2, osrc2, cnt2 = spawn(order=order)
+        assert out2[:m].cpu().numpy().tobytes() == g.tobytes() and np.array_equal(osrc2, src), what
+        ordh = order[:m].cpu().numpy().astype(np.int64)
+        assert np.array_equal(np.sort(ordh), np.arange(m)), what
+        same_occ(any_hit(out2, order, cnt2), ref, (what, "ordered"))
+        # traced: the rays written in that order
+        out3, osrc3, cnt3 = spawn(traced=True)
+        assert out3[:m].cpu().numpy().tobytes() == g[ordh].tobytes(), what
+        assert np.array_equal(osrc3, src[ordh]), what
+        same_occ(any_hit(out3, None, cnt3), ref[ordh], (what, "traced"))
+        # pairs: the traced order's (source, sample) pairs, the rays made in the lanes
+        first = np.searchsorted(src, src)  # a hit spawns its samples in order
+        sample = (np.arange(m) - first)[ordh]
+        for fused in (False, True):
+            pairs = T.full((n * ns,), -1, dtype=T.int32, device="cuda")
+            lv = T.full((npix * ns, 4), float("nan"), dtype=T.float32, device="cuda")
+            rec = T.full((n, 16), float("nan"), dtype=T.float32, device="cuda")
+            pcnt = T.full((1,), 123, dtype=T.int32, device="cuda")
+            occ = T.full((n * ns,), 9, dtype=T.uint8, device="cuda")
+            if fused:
+                e.rt.occluded_ao(rays, h, pixid, n, ns, pairs, lv, rec, pcnt, occ)
+            else:
+                e.rt.spawn_shadows_ao_pairs(rays, h, pixid, n, ns, pairs, lv, rec, pcnt)
+                e.rt.occluded_ao_pairs(n * ns, pairs, rec, lv, ns, pcnt, occ)
+            e.rt.sync()
+            assert int(pcnt.item()) == m, (what, fused)
+            fp = pairs[:m].cpu().numpy().view(np.uint32)
+            assert np.array_equal((fp >> 5).astype(np.int64), src[ordh]), (what, fused)
+            per = np.bincount(src, minlength=n)
+            if (per[per > 0] == ns).all():  # every hit spawned every sample
+                assert np.array_equal((fp & 31).astype(np.int64), sample), (what, fused)
+            key = (fp >> 5).astype(np.int64) * 64 + (fp & 31)  # each sample of a source once
+            assert len(np.unique(key)) == m and ((fp & 31) < ns).all(), (what, fused)
+            o = occ.cpu().numpy()
+            same_occ(o[:m], ref[ordh], (what, fused, "pairs"))
+            assert (o[m:] == 9).all(), (what, fused)
+    finally:
+        e.rt.set_coherence(e.rt.RAYS_ADAPTIVE)
+
+
 # ---- the tests ----
+def test_occluded_scene_order(env):
+    for name in NAMES:
+        form_occluded_order(env, name)
+
+
+def test_occluded_scene_devcount(env):
+    for name in NAMES:
+        form_occluded_devcount(env, name)
+
+
+def test_spawn_shadows_pt(env):
+    for name in NAMES:
+        form_spawn_pt(env, name)
+
+
+@pytest.mark.parametrize("ns", [4, 16])
+def test_ao_chain(env, ns):
+    """On the hits of `surface` (origins on coincident triangles), `edge` and
+    `mixed`: at 1e4 the AO origin and frame are where the pairs form's
+    16-float record must reproduce the written ray's bits."""
+    for name in ("surface", "edge", "mixed"):
+        form_ao(env, name, ns)
+
+
 def test_per_slot_streams(env):
     """intersect1M / occluded1M of every slot, every class."""
     for name in NAMES:
