@@ -1170,10 +1170,15 @@ int spray_rt_insitu_trace_camera(spray_rt_insitu_t ins, const spray_rt_shader* s
 /* The image-parallel frame of a camera (the reference's ooc
  * mode shards as replicas -- any rank may hold any domain -- and only the
  * image is composited): EVERY domain resident on every rank (ERR_STATE
- * otherwise), the image_h rows cut into world * bands horizontal bands of
- * equal height (bands > 1: image_h divisible by world * bands), rank r
- * owns bands r, r + world, ... (bands = 1: makeHorizontalStripe,
- * tile.cc:187-209).  Each rank generates its bands' eye rays
+ * otherwise), the image_h rows cut into world * bands horizontal bands,
+ * band b = rows [b image_h / (world bands), (b + 1) image_h / (world bands)),
+ * rank r owns bands r, r + world, ... (bands = 1, world | image_h:
+ * makeHorizontalStripe, tile.cc:187-209).  Band heights may differ by one row, except where
+ * world > 1, bands > 1 and the bands are traced whole (spp does not divide
+ * 64, or SPRAY_IMAGE_CULL=0): that gather copies equal bands, so image_h
+ * must be divisible by world * bands -- ERR_ARG otherwise, decided from the
+ * arguments before anything is launched, written or sent (the image and
+ * the collective log stay as they were, on every rank alike).  Each rank generates its bands' eye rays
  * (insitu::genMultiSampleEyeRays seeds: (pixel, sample), so any split
  * gives every pixel the same bits), traces them with the all-local frame of
  * world 1 (any shading spray_rt_insitu_trace supports: the fused PT launch,

@@ -2214,6 +2214,10 @@ int spray_rt_insitu_trace_image(spray_rt_insitu_t I, const spray_rt_shader* P,
   // spp trace the bands whole.
   const char* ce = std::getenv("SPRAY_IMAGE_CULL");
   const bool cull = 64 % spp == 0 && !(ce && ce[0] == '0');
+  // whole bands are gathered by 2-D copies of equal bands: refused here,
+  // from arguments every rank shares, before any launch or collective
+  if (W > 1 && bands > 1 && !cull && image_h % bt)
+    return fail(c, SPRAY_RT_ERR_ARG, "interleaved bands need %d | %d rows", bt, image_h);
   if (cull) {
     r = prepare_image(I, cam, image_w, image_h, bands);
     if (r) return r;
@@ -2254,6 +2258,13 @@ int spray_rt_insitu_trace_image(spray_rt_insitu_t I, const spray_rt_shader* P,
   auto gather = [&]() -> int {
     if (W == 1) return SPRAY_RT_OK;
     std::vector<size_t> sb(size_t(W), 0), rb(size_t(W), 0);
+    auto tally = [&]() {  // the stats' bytes to and from the other ranks
+      for (int k = 0; k < W; ++k)
+        if (k != I->rank) {
+          I->st[0] += sb[size_t(k)];
+          I->st[1] += rb[size_t(k)];
+        }
+    };
     if (cull) {
       // the RGB of the U pixels only (the film writes nothing else): rank k
       // packs its table's pixels, rank 0 unpacks the others' in rank order
@@ -2262,6 +2273,7 @@ int spray_rt_insitu_trace_image(spray_rt_insitu_t I, const spray_rt_shader* P,
       GROW(I->gpack, I->rank == 0 ? size_t(I->tg.npix) * 12 + 16 : sb[0] + 16);
       float* pk = I->gpack.as<float>();
       if (I->rank != 0) HIPCHK(c, launch_pack_rgb(s, I->ti, image_w, image, pk));
+      tally();
       COMM(I->tr->alltoallv(I, pk, sb.data(), pk, rb.data(), true));
       if (I->rank == 0) HIPCHK(c, launch_unpack_rgb(s, I->tg, image_w, pk, image));
       return SPRAY_RT_OK;
@@ -2275,18 +2287,18 @@ int spray_rt_insitu_trace_image(spray_rt_insitu_t I, const spray_rt_shader* P,
       for (int k = 0; k < W; ++k) rb[size_t(k)] = rrows[size_t(k)] * row * 4;
     if (bands == 1) {
       float* base = image + size_t(mine.front().first) * row;
+      tally();
       COMM(I->tr->alltoallv(I, base, sb.data(), image, rb.data(), true));
       return SPRAY_RT_OK;
     }
-    const size_t band_b = size_t(band_row(1, bt, image_h)) * row * 4;  // uniform bands only
-    for (int b = 0; b < bt; ++b)
-      if (size_t(band_row(b + 1, bt, image_h) - band_row(b, bt, image_h)) * row * 4 != band_b)
-        return fail(c, SPRAY_RT_ERR_ARG, "interleaved bands need %d | %d rows", bt, image_h);
+    // equal bands (bt | image_h: checked before the frame was traced)
+    const size_t band_b = size_t(band_row(1, bt, image_h)) * row * 4;
     const size_t total = size_t(image_h) * row * 4;
     GROW(I->gpack, I->rank == 0 ? total : mine_b);
     char* pk = I->gpack.as<char>();
     // band k of this rank sits at row (rank + k W) * band rows
     if (I->rank != 0) HIPCHK(c, launch_bands_copy(s, image, pk, W, bands, band_b, I->rank, 1, 1));
+    tally();
     COMM(I->tr->alltoallv(I, pk, sb.data(), pk, rb.data(), true));
     if (I->rank == 0)  // rank k's segment: its bands, in order
       HIPCHK(c, launch_bands_copy(s, image, pk, W, bands, band_b, 1, W - 1, 0));

@@ -264,3 +264,35 @@ def test_fused_frame_cull_matches_whole_tiles(spray, oracle, scene64, monkeypatc
         assert out[0][1] == out[1][1] and out[0][1][0] == w * h * spp
         assert out[0][0].tobytes() == out[1][0].tobytes()
     assert out[0][1][1] == 0 and not out[0][0].any()  # the camera facing away
+
+
+# Off the square: widths and heights that are no multiple of 4 or of 64, and
+# two tiles that neither cover the image nor start at its origin, so a
+# width / height mix-up or a tile offset dropped moves pixels.
+WIDE = (90, 50)
+TALL = (50, 90)
+SHAPE_TILES = {WIDE: [(7, 5, 40, 30), (47, 11, 36, 37)],
+               TALL: [(3, 9, 30, 41), (11, 50, 37, 38)]}
+
+
+@pytest.mark.parametrize("shape", [WIDE, TALL], ids=["wide", "tall"])
+@pytest.mark.parametrize("kind,bounces,samples,spp", [("pt", 2, 1, 3), ("ao", 1, 4, 2)])
+def test_frame_off_the_square(spray, oracle, scene64, kind, bounces, samples, spp, shape):
+    """PT with 2 bounces at spp 3 and AO with 4 samples at spp 2 on 90x50 and
+    50x90: the image bit-identical to the oracle's, the counts equal.
+    Recorded on the oracle: each tile shades > 1000 shadow rays, 509 to 1486
+    pixels lit per case."""
+    w, h = shape
+    tiles = SHAPE_TILES[shape]
+    img, ref, cnt, (nrad, nsh, bad) = render_both(spray, oracle, scene64, kind, bounces, samples,
+                                                  spp, tiles, w=w, h=h)
+    assert bad == 0
+    lit = ref.reshape(h, w, 4)[..., :3].sum(-1) > 0
+    assert lit.sum() > 300
+    covered = np.zeros((h, w), bool)
+    for x, y, tw, th in tiles:
+        assert lit[y:y + th, x:x + tw].sum() > 100  # both tiles see the scene
+        covered[y:y + th, x:x + tw] = True
+    assert not lit[~covered].any() and not covered.all()
+    assert img.tobytes() == ref.tobytes()
+    assert cnt == (nrad, nsh)

@@ -92,7 +92,7 @@ def _rendezvous_file():
     return p
 
 
-CASES = {  # name: (shader kind, bounces, samples, image size, spp)
+CASES = {  # name: (shader kind, bounces, samples, image size (a side or (w, h)), spp)
     "pt1": ("pt", 1, 1, 128, 2),
     "ao16": ("ao", 1, 16, 64, 2),
     "pt3": ("pt", 3, 2, 96, 2),
@@ -109,6 +109,16 @@ CAMERAS = {"pt1-eyein": dict(pos=[9.0, 8.5, -9.0], lookat=[30.0, 28.649426, 30.0
                              up=[0.0, 1.0, 0.0], fov=90.0)}  # domain 0's box: +-10
 
 
+def _wh(img):
+    """An image size: a square's side or (w, h)."""
+    return (img, img) if isinstance(img, int) else (int(img[0]), int(img[1]))
+
+
+def _spec(table, case):
+    """A case by name, or its tuple itself (other files' shapes)."""
+    return table[case] if isinstance(case, str) else tuple(case)
+
+
 def _engine_rank(rank, world, case, transport, dist=None, one_owner=False, replicated=False,
                  mode=0, scene=None, owner=None):
     """One rank's engine frame of CASES[case]: returns (records, totals, image).
@@ -121,9 +131,10 @@ def _engine_rank(rank, world, case, transport, dist=None, one_owner=False, repli
     from spray_amd import insitu
     from oracle import pyoracle as po
     from test_insitu import scene_boxes
-    kind, bounces, samples, img, spp = CASES[case]
+    kind, bounces, samples, img, spp = _spec(CASES, case)
+    w, h = _wh(img)
     c = CAMERAS.get(case, H.BENCH_CAMERA)
-    cam = spray_amd.camera_init(c["pos"], c["lookat"], c["up"], c["fov"], img, img)
+    cam = spray_amd.camera_init(c["pos"], c["lookat"], c["up"], c["fov"], w, h)
     scene = scene or WAVELETS64
     if owner is None:
         boxes, bound = scene_boxes()
@@ -135,21 +146,21 @@ def _engine_rank(rank, world, case, transport, dist=None, one_owner=False, repli
     insitu.setup_rank_context(rt, scene, SCENES, owner, rank)
     rt.set_bsdfs(spray_amd.engine.host_scene_bsdfs(scene))
     rt.set_stream(torch.cuda.current_stream())
-    block = (0, 0, img, img)
+    block = (0, 0, w, h)
     stripe = block if replicated else insitu.horizontal_stripe(world, rank, block)
     n = stripe[2] * stripe[3] * spp
     rays = torch.empty((max(n, 1), 8), dtype=torch.float32, device="cuda")[:n]
     pix = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
     sam = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")[:n]
-    rt.eye_rays_insitu(cam, img, spp, block, stripe, rays, pix, sam)
+    rt.eye_rays_insitu(cam, w, spp, block, stripe, rays, pix, sam)
     lights = LIGHTS.get(case, [(0, 0.0, 500.0, 1000.0, 1.0, 1.0, 1.0)])
     sh = spray_amd.frame.make_shader(kind, bounces, samples, lights=lights)
     eng = insitu.InsituEngine(rt, world, rank, dist=dist, transport=transport)
-    recs = insitu.InsituRecords(img * img * spp * bounces + 16)
-    image = torch.zeros(img * img * 4, dtype=torch.float32, device="cuda")
+    recs = insitu.InsituRecords(w * h * spp * bounces + 16)
+    image = torch.zeros(w * h * 4, dtype=torch.float32, device="cuda")
     if replicated == "camera":
         def trace(sh, rays, pix, sam, spp, image, recs=None):
-            return eng.trace_camera(sh, cam, img, img, spp, image, recs)
+            return eng.trace_camera(sh, cam, w, h, spp, image, recs)
     else:
         trace = eng.trace_frame if replicated else eng.trace
     eng.set_timing(True)
@@ -169,13 +180,14 @@ def _engine_rank(rank, world, case, transport, dist=None, one_owner=False, repli
 
 
 def _reference(oracle, case):
-    kind, bounces, samples, img, spp = CASES[case]
+    kind, bounces, samples, img, spp = _spec(CASES, case)
+    w, h = _wh(img)
     c = CAMERAS.get(case, H.BENCH_CAMERA)
-    cam = oracle.camera_init(c["pos"], c["lookat"], c["up"], c["fov"], img, img)
+    cam = oracle.camera_init(c["pos"], c["lookat"], c["up"], c["fov"], w, h)
     _, doms, _ = oracle.load_scene(WAVELETS64, SCENES)
     sh = H.insitu_shader(oracle, kind, bounces, samples, LIGHTS.get(case))
-    return H.reference_frame(oracle, sh, oracle.scene_bsdfs(doms), cam, img, img, spp,
-                             (0, 0, img, img))
+    return H.reference_frame(oracle, sh, oracle.scene_bsdfs(doms), cam, w, h, spp,
+                             (0, 0, w, h))
 
 
 def same_collectives(results):
@@ -666,9 +678,10 @@ def _image_frame(rank, world, case, transport, dist=None, bands=1, how="image"):
     image's eye rays through spray_rt_insitu_trace (how "rays").  Returns (records, totals, image, stats)."""
     import spray_amd
     from spray_amd import insitu
-    kind, bounces, samples, img, spp, lights = IMG_CASES[case]
+    kind, bounces, samples, img, spp, lights = _spec(IMG_CASES, case)
+    w, h = _wh(img)
     c = H.BENCH_CAMERA
-    cam = spray_amd.camera_init(c["pos"], c["lookat"], c["up"], c["fov"], img, img)
+    cam = spray_amd.camera_init(c["pos"], c["lookat"], c["up"], c["fov"], w, h)
     rt = spray_amd.RtContext(0)
     nd = len(spray_amd.engine.host_parse_scene(WAVELETS64, SCENES)[0])
     insitu.setup_rank_context(rt, WAVELETS64, SCENES, np.full(nd, rank, np.int32), rank)
@@ -676,16 +689,16 @@ def _image_frame(rank, world, case, transport, dist=None, bands=1, how="image"):
     rt.set_stream(torch.cuda.current_stream())
     sh = spray_amd.frame.make_shader(kind, bounces, samples, lights=lights)
     eng = insitu.InsituEngine(rt, world, rank, dist=dist, transport=transport)
-    recs = insitu.InsituRecords(img * img * spp * bounces + 16)
-    image = torch.zeros(img * img * 4, dtype=torch.float32, device="cuda")
+    recs = insitu.InsituRecords(w * h * spp * bounces + 16)
+    image = torch.zeros(w * h * 4, dtype=torch.float32, device="cuda")
     if how == "image":
-        tot = eng.trace_image(sh, cam, img, img, spp, image, bands, recs)
+        tot = eng.trace_image(sh, cam, w, h, spp, image, bands, recs)
     else:  # the whole image's stored eye rays through the one-rank all-local frame
-        n = img * img * spp
+        n = w * h * spp
         rays = torch.empty((n, 8), dtype=torch.float32, device="cuda")
         pix = torch.empty(n, dtype=torch.int32, device="cuda")
         sam = torch.empty(n, dtype=torch.int32, device="cuda")
-        rt.eye_rays_insitu(cam, img, spp, (0, 0, img, img), (0, 0, img, img), rays, pix, sam)
+        rt.eye_rays_insitu(cam, w, spp, (0, 0, w, h), (0, 0, w, h), rays, pix, sam)
         tot = eng.trace(sh, rays, pix, sam, spp, image, recs)
     torch.cuda.synchronize()
     st = eng.stats()
@@ -713,13 +726,14 @@ def _image_rank_main(rank, world, port, out, case, bands):
 
 
 def _image_reference(oracle, case):
-    kind, bounces, samples, img, spp, lights = IMG_CASES[case]
+    kind, bounces, samples, img, spp, lights = _spec(IMG_CASES, case)
+    w, h = _wh(img)
     c = H.BENCH_CAMERA
-    cam = oracle.camera_init(c["pos"], c["lookat"], c["up"], c["fov"], img, img)
+    cam = oracle.camera_init(c["pos"], c["lookat"], c["up"], c["fov"], w, h)
     _, doms, _ = oracle.load_scene(WAVELETS64, SCENES)
     sh = H.insitu_shader(oracle, kind, bounces, samples, lights)
-    return H.reference_frame(oracle, sh, oracle.scene_bsdfs(doms), cam, img, img, spp,
-                             (0, 0, img, img))
+    return H.reference_frame(oracle, sh, oracle.scene_bsdfs(doms), cam, w, h, spp,
+                             (0, 0, w, h))
 
 
 @pytest.mark.parametrize("world,bands,case", [(1, 1, "pt1"), (1, 2, "ao16"), (2, 1, "pt1"),
