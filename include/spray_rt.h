@@ -605,6 +605,104 @@ int spray_rt_cell_split_host(const spray_rt_cellmesh* mesh, size_t* ntets, uint3
 int spray_rt_cell_isosurface_host(const spray_rt_cellmesh* mesh, const spray_rt_grid_color* gcolor,
                                   size_t* nverts, size_t* nfaces, float* verts_out,
                                   float* vnormals_out, uint32_t* colors_out, uint32_t* faces_out);
+/* ---- boundary surfaces and thresholds of cell meshes ---- */
+/* Which cells of a spray_rt_cellmesh a surface extraction keeps. */
+#define SPRAY_RT_SELECT_ALL    0  /* every cell */
+#define SPRAY_RT_SELECT_POINTS 1  /* cells all of whose points have lo <= values[p] <= hi */
+#define SPRAY_RT_SELECT_CELLS  2  /* cells with lo <= cell_values[i] <= hi */
+typedef struct spray_rt_cell_select {
+  const float* cell_values;  /* [ncells], device or host; read in mode CELLS only */
+  float lo, hi;              /* lo <= hi, both finite (modes POINTS, CELLS) */
+  int32_t mode;
+} spray_rt_cell_select;
+/* The outer surface of the kept cells of a mesh, as an indexed triangle mesh
+ * over the mesh's own points: with SPRAY_RT_SELECT_ALL the mesh's boundary,
+ * with a range the threshold solid with its cut faces.  The rule is fixed, so
+ * that the kernels and the host restatement agree byte for byte (DESIGN.md
+ * section 16).  mesh.isovalue is ignored; mesh.values is read, and may be NULL
+ * otherwise, only in mode POINTS.
+ *
+ * Kept cells: all; those whose listed points all have lo <= values[p] &&
+ * values[p] <= hi; those with lo <= cell_values[i] && cell_values[i] <= hi.
+ * Only kept cells have faces: a hex, wedge or pyramid those of the tables of
+ * spray_rt_cell_isosurface in their order, a tet (0,1,2) (0,1,3) (1,2,3)
+ * (2,0,3).  With c[i] = P[q[i]] the point indices of a face and j the position
+ * of the smallest (the lowest j on ties), a triangle has a = c[(j+1)%3], b =
+ * c[(j+2)%3], a quad a = c[(j+1)%4], b = c[(j+3)%4], and the face's key is its
+ * corner count with the triple (c[j], min(a,b), max(a,b)).  A face is on the
+ * surface when its key occurs exactly once among the kept cells' faces of its
+ * mesh; keys that occur twice or more are dropped, duplicate cells included.
+ * Faces match only as whole faces: a triangle never matches a quad, so where a
+ * quad of one cell meets the two triangles of a split neighbour (a
+ * non-conforming interface), along either diagonal, all three faces are
+ * emitted, as VTK's surface filter does.
+ *
+ * Vertices are the distinct points the surviving faces use, ascending by point
+ * index: position and normal are the point's own bytes, the colour is
+ * map(g[p]) with spray_rt_grid_color's rule (its field is [npoints]) or
+ * color_rgb, and point_ids[v] is the point's index, so that a caller can gather
+ * another field, map it with spray_rt_colormap_apply and recolour the slot with
+ * spray_rt_domains_recolor.  Triangles come per cell in input order, then per
+ * face in table order: a triangle face is (c0,c1,c2); a quad gives (r0,r1,r2)
+ * then (r0,r2,r3) with r_d = c[(j+d)%4], the diagonal of the tet split of
+ * spray_rt_cell_isosurface, so the surface is exactly the boundary of that
+ * split and an isosurface of the same mesh meets it without cracks.  Faces are
+ * turned outward from the geometry: with pref the cell's point at the lowest
+ * local position not on the face and det = dot(cross(p1 - p0, p2 - p0), pref -
+ * p0) on the face's first triangle, term by term in float as for the tets'
+ * parity, det < 0 swaps the last two corners of the face's one or two
+ * triangles; then Ng = (v0 - v1) x (v2 - v0) points away from pref.  det == 0
+ * and NaN leave the listed order; one decision per face.  A cell that lists a
+ * point twice goes through the same rule; zero-area triangles are kept.  No
+ * atomic and no hash decides an index: two runs give the same bytes.
+ *
+ * spray_rt_cell_surface has the argument shapes and NULL conventions of
+ * spray_rt_cell_isosurface, with selects (NULL: every cell of every mesh) and
+ * point_ids beside them: any output or single entry may be NULL, all NULL only
+ * counts, a capacity that is too small gives SPRAY_RT_ERR_LIMIT with the
+ * counts reported and no buffer written.  Two host reads per call: status and
+ * the face-instance totals, then the vertex and triangle counts.
+ *
+ * SPRAY_RT_ERR_ARG, before anything is written and naming the mesh: an unknown
+ * mode, lo > hi or a non-finite bound (modes POINTS and CELLS), a NULL array
+ * the mode reads (ncells == 0 reads nothing and gives the empty surface), a
+ * bad colour map, vnormals[i] non-NULL for a mesh without point_normals, and
+ * for every cell, kept or not: an unknown type, offsets that do not match it
+ * or pass nconn, a point index >= npoints, a non-finite value among what the
+ * call reads of a referenced point (coordinates, values in mode POINTS, the
+ * colour sample of a mapped mesh, the normal where normals are written), a
+ * non-finite cell_values[i] in mode CELLS.  Points no cell references are
+ * never read.  SPRAY_RT_ERR_LIMIT: npoints > 2^21 (the three-index key must
+ * fit 64 bits; a two-pass sort for larger meshes is left out on purpose),
+ * ncells >= 2^29, nconn >= 2^32, 2^32 or more face instances in one call, more
+ * than 65,535 meshes. */
+int spray_rt_cell_surface(spray_rt_ctx_t ctx, int n, const spray_rt_cellmesh* meshes,
+                          const spray_rt_cell_select* selects, const spray_rt_grid_color* gcolors,
+                          float* const* verts, float* const* vnormals, uint32_t* const* colors,
+                          uint32_t* const* point_ids, uint32_t* const* faces,
+                          const size_t* cap_verts, const size_t* cap_faces, size_t* nverts_out,
+                          size_t* nfaces_out);
+/* Meshes in, resident slots out, as spray_rt_domains_cell_isosurface: slots[i]
+ * is byte for byte a slot of spray_rt_domains_build of the extracted mesh.  At
+ * most four host reads (the extraction's two and the build's two).  A failed
+ * call leaves every slot as it was; messages name the mesh and its slot.  Not
+ * for use while lanes run. */
+int spray_rt_domains_cell_surface(spray_rt_ctx_t ctx, int n, const int* slots,
+                                  const spray_rt_cellmesh* meshes,
+                                  const spray_rt_cell_select* selects,
+                                  const spray_rt_grid_color* gcolors, int with_normals,
+                                  float* d_bounds, size_t* nfaces_out);
+/* Host-only restatement (no GPU; every array is host memory): the arrays the
+ * kernels write, byte for byte.  select and gcolor may be NULL; any output may
+ * be NULL; vnormals_out needs point_normals. */
+int spray_rt_cell_surface_host(const spray_rt_cellmesh* mesh, const spray_rt_cell_select* select,
+                               const spray_rt_grid_color* gcolor, size_t* nverts, size_t* nfaces,
+                               float* verts_out, float* vnormals_out, uint32_t* colors_out,
+                               uint32_t* point_ids_out, uint32_t* faces_out);
+/* Where the last surface extraction of the context spent its time, as
+ * spray_rt_tet_phase_times (the sort's device time while
+ * spray_rt_tet_set_timing is on). */
+int spray_rt_cell_surface_phase_times(spray_rt_ctx_t ctx, double out_ms[4]);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes

@@ -79,6 +79,15 @@ class CellMesh(C.Structure):
 
 assert C.sizeof(CellMesh) == 88
 
+
+class CellSelect(C.Structure):
+    """spray_rt_cell_select."""
+    _fields_ = [("cell_values", C.c_void_p), ("lo", C.c_float), ("hi", C.c_float),
+                ("mode", C.c_int32)]
+
+
+assert C.sizeof(CellSelect) == 24
+
 # every symbol the public headers declare: (restype, argtypes)
 P = C.c_void_p
 SZ = C.c_size_t
@@ -121,6 +130,10 @@ SIGNATURES = {
     "spray_rt_cell_isosurface_host": (I, [P, P, P, P, P, P, P, P]),
     "spray_rt_cell_split_host": (I, [P, P, P]),
     "spray_rt_cell_phase_times": (I, [P, P]),
+    "spray_rt_cell_surface": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_cell_surface": (I, [P, I, P, P, P, P, I, P, P]),
+    "spray_rt_cell_surface_host": (I, [P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_cell_surface_phase_times": (I, [P, P]),
     "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
     "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),

@@ -409,10 +409,11 @@ int spray_rt_destroy(spray_rt_ctx_t c) {
   void* bufs[] = {c->d_slots, c->d_boxes, c->d_dom2slot, c->d_domtrav, c->d_owner, c->d_tlas, c->d_seg_slot,
                   c->d_seg_off, c->d_stage, c->d_stage2, c->d_stage3,
                   c->d_block_counts, c->d_heads, c->d_sel, c->d_bsdf, c->d_frame, c->d_fstats, c->d_ftab,
-                  c->d_sah, c->d_sort, c->d_isomesh, c->d_tetinst, c->d_celltets};
+                  c->d_sah, c->d_sort, c->d_isomesh, c->d_tetinst, c->d_celltets, c->d_surfinst};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
-  for (JobArena* a : {&c->refit, &c->build, &c->iso, &c->recolor, &c->tet, &c->cell}) arena_release(a);
+  for (JobArena* a : {&c->refit, &c->build, &c->iso, &c->recolor, &c->tet, &c->cell, &c->surf})
+    arena_release(a);
   if (c->recolor_copied) (void)hipEventDestroy(c->recolor_copied);
   for (hipEvent_t e : c->tet_ev)
     if (e) (void)hipEventDestroy(e);

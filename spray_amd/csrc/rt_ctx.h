@@ -105,6 +105,10 @@ struct spray_rt_ctx {
   void* d_celltets = nullptr;       // cell isosurface: the tets of the crossing cells
   size_t celltets_cap = 0;
   double cell_ms = 0.0;  // spray_rt_cell_phase_times: wall clock to the cell pass's host read
+  spray_rt::detail::JobArena surf;  // job tables, records | staged mesh arrays, cell and point scratch
+  void* d_surfinst = nullptr;       // cell surface: the per-face-instance scratch (keys, flags)
+  size_t surfinst_cap = 0;
+  double surf_ms[4] = {};  // spray_rt_cell_surface_phase_times, as tet_ms
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;

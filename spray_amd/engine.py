@@ -13,12 +13,12 @@ import ctypes as C
 import numpy as np
 
 from ._native import (HIT_DTYPE, INVALID_ID, RAY_DTYPE, RTC_ISECT_DTYPE, BsdfRec,
-                      SprayRtError, CellMesh, TetMesh, lib)
+                      SprayRtError, CellMesh, CellSelect, TetMesh, lib)
 
 __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_rays",
            "bvh_refit_host", "bvh_build_device_host", "isosurface_host",
            "isosurface_mapped_host", "colormap_host", "tet_isosurface_host",
-           "cell_isosurface_host", "cell_split_host", "SLOT_COLORS",
+           "cell_isosurface_host", "cell_split_host", "cell_surface_host", "SLOT_COLORS",
            "SLOT_FACES",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
@@ -405,13 +405,14 @@ def _cell_list(x, dtype, what):
     return x, x.size
 
 
-def _cell_table(meshes):
+def _cell_table(meshes, contoured=True):
     """Dicts with "points" (float32 [np, 3]), "types" (uint8 [nc], the
     SPRAY_RT_CELL_* = VTK codes), "offsets" (uint32 [nc + 1]), "conn" (uint32
     [nconn]), "values" (float32 [np]), "iso" and optionally "normals", "color",
     "cfield" with "cmap" as in _tet_table -> (spray_rt_cellmesh array,
     spray_rt_grid_color array, keepalive).  Arrays are numpy arrays or torch
-    tensors on the GPU."""
+    tensors on the GPU.  contoured False: "values" and "iso" are optional (a
+    NULL pointer, isovalue 0)."""
     arr = (CellMesh * max(len(meshes), 1))()
     carr = (_GridColor * max(len(meshes), 1))()
     keep = []
@@ -423,9 +424,11 @@ def _cell_table(meshes):
 
     for m, rec, crec in zip(meshes, arr, carr):
         points, npts = _tet_array(m["points"], np.float32, 3, "points")
-        values, nval = _tet_array(m["values"], np.float32, 0, "values")
-        if nval != npts:
-            raise ValueError("cell_isosurface: one value per point")
+        values = None
+        if contoured or m.get("values") is not None:
+            values, nval = _tet_array(m["values"], np.float32, 0, "values")
+            if nval != npts:
+                raise ValueError("cell_isosurface: one value per point")
         types, ncells = _cell_list(m["types"], np.uint8, "types")
         offsets, noff = _cell_list(m["offsets"], np.uint32, "offsets")
         conn, nconn = _cell_list(m["conn"], np.uint32, "conn")
@@ -439,7 +442,7 @@ def _cell_table(meshes):
             if nn != npts:
                 raise ValueError("cell_isosurface: one normal per point")
             rec.point_normals = put(nrm)
-        rec.isovalue = float(m["iso"])
+        rec.isovalue = float(m["iso"] if contoured else m.get("iso", 0.0))
         color = m.get("color")
         rec.has_color = 0 if color is None else 1
         rec.color_rgb = 0 if color is None else int(color)
@@ -507,6 +510,67 @@ def cell_isosurface_host(points, types, offsets, conn, values, iso, normals=None
     f = np.zeros((nf.value, 3), np.uint32)
     call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, f.ctypes.data)
     return v, n, c, f
+
+
+SELECT_MODES = {"all": 0, "points": 1, "cells": 2}
+
+
+def _surf_table(meshes, selects):
+    """Mesh dicts as in _cell_table, where "values" and "iso" are optional
+    ("values" is needed by a "points" select only), with selects parallel to
+    them (None: every cell of every mesh): None for every cell, or a dict with
+    "mode" ("all", "points", "cells" or the SPRAY_RT_SELECT_* number), "lo",
+    "hi" and, for "cells", "cell_values" (float32 [ncells], numpy or a torch
+    tensor on the GPU) -> (spray_rt_cellmesh array, spray_rt_cell_select array,
+    spray_rt_grid_color array, keepalive)."""
+    if selects is not None and len(selects) != len(meshes):
+        raise ValueError("cell_surface: one select per mesh")
+    sarr = (CellSelect * max(len(meshes), 1))()
+    arr, carr, keep = _cell_table(meshes, contoured=False)
+    for i in range(len(meshes)):
+        sel = selects[i] if selects is not None else None
+        if sel is None:
+            continue
+        mode = sel.get("mode", "all")
+        sarr[i].mode = SELECT_MODES[mode] if isinstance(mode, str) else int(mode)
+        sarr[i].lo, sarr[i].hi = float(sel.get("lo", 0.0)), float(sel.get("hi", 0.0))
+        if sel.get("cell_values") is not None:
+            cv, ncv = _tet_array(sel["cell_values"], np.float32, 0, "cell values")
+            if ncv != arr[i].ncells:
+                raise ValueError("cell_surface: one cell value per cell")
+            a, k = _addr(cv)
+            keep.append(k)
+            sarr[i].cell_values = a
+    return arr, sarr, carr, keep
+
+
+def cell_surface_host(points, types, offsets, conn, select=None, values=None, normals=None,
+                      cfield=None, cmap=None, color=None):
+    """spray_rt_cell_surface_host (no GPU): the boundary surface of the cells
+    a select keeps (see _surf_table; numpy arrays) -> (verts float32 [nv, 3],
+    normals float32 [nv, 3] or None without point normals, colors uint32 [nv],
+    point_ids uint32 [nv], faces uint32 [nf, 3])."""
+    m = dict(points=points, types=types, offsets=offsets, conn=conn, values=values,
+             normals=normals, cfield=cfield, cmap=cmap, color=color)
+    arr, sarr, carr, keep = _surf_table([m], [select])
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_cell_surface_host(C.addressof(arr), C.addressof(sarr), C.addressof(carr),
+                                          C.byref(nv), C.byref(nf), *outs)
+        if rc != 0:
+            _cell_fail("cell_surface_host", rc)
+
+    call(None, None, None, None, None)
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals is not None else None
+    c = np.zeros(nv.value, np.uint32)
+    ids = np.zeros(nv.value, np.uint32)
+    f = np.zeros((nf.value, 3), np.uint32)
+    call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, ids.ctypes.data,
+         f.ctypes.data)
+    return v, n, c, ids, f
 
 
 def host_parse_scene(desc, ply_path=""):
@@ -1080,6 +1144,96 @@ class RtContext:
         cell pass's host read, then tet_phase_times' four from there on]."""
         out = (C.c_double * 5)()
         self._check(lib().spray_rt_cell_phase_times(self.h, out), "cell_phase_times")
+        return list(out)
+
+    # ---- boundary surfaces and thresholds of cell meshes ----
+    def cell_surface(self, meshes, selects=None, normals=True, capacity=None, count_only=False):
+        """spray_rt_cell_surface: the boundary surfaces of the cells the selects
+        keep (see _surf_table) in one batched call -> [(verts float32 [nv, 3],
+        normals float32 [nv, 3] or None (normals False, or a mesh without them),
+        colors int32 [nv] holding the 0x00RRGGBB bits, point_ids int32 [nv],
+        faces int32 [nf, 3] holding the uint32 bits)] as GPU tensors of the
+        exact sizes (a counting call first).  capacity and count_only as in
+        tet_isosurface.  Enqueued on the context's stream."""
+        import torch
+        fn = lib().spray_rt_cell_surface
+        n = len(meshes)
+        arr, sarr, carr, keep = _surf_table(meshes, selects)
+        sel = None if selects is None else sarr
+        m = max(n, 1)
+        nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        if capacity is None or count_only:
+            self._check(fn(self.h, n, arr, sel, carr, None, None, None, None, None, None, None,
+                           nv, nf), "cell_surface")
+            caps = [(nv[i], nf[i]) for i in range(n)]
+            if count_only:
+                return caps
+        else:
+            caps = [(int(capacity[0]), int(capacity[1]))] * n
+        dev = "cuda:%d" % self._device
+        # zeroed, one element at least: a buffer a failed call must not touch
+        v = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) for cv, _ in caps]
+        nr = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev)
+              if normals and meshes[i].get("normals") is not None else None
+              for i, (cv, _) in enumerate(caps)]
+        col = [torch.zeros(max(cv, 1), dtype=torch.int32, device=dev) for cv, _ in caps]
+        ids = [torch.zeros(max(cv, 1), dtype=torch.int32, device=dev) for cv, _ in caps]
+        f = [torch.zeros((max(cf, 1), 3), dtype=torch.int32, device=dev) for _, cf in caps]
+
+        def ptrs(xs):
+            if all(x is None for x in xs):
+                return None
+            return (C.c_void_p * m)(*[None if x is None else x.data_ptr() for x in xs])
+
+        _fills_done()
+        try:
+            self._check(fn(
+                self.h, n, arr, sel, carr, ptrs(v), ptrs(nr), ptrs(col), ptrs(ids), ptrs(f),
+                (C.c_size_t * m)(*[c[0] for c in caps]), (C.c_size_t * m)(*[c[1] for c in caps]),
+                nv, nf), "cell_surface")
+        except SprayRtError as e:
+            e.counts = [(nv[i], nf[i]) for i in range(n)]
+            e.buffers = (v, [x for x in nr if x is not None], col, ids, f)
+            raise
+        cut = lambda x, k: None if x is None else x[:k]
+        return [(v[i][:nv[i]], cut(nr[i], nv[i]), col[i][:nv[i]], ids[i][:nv[i]], f[i][:nf[i]])
+                for i in range(n)]
+
+    def cell_surface_domains(self, slots, meshes, selects=None, normals=True, bounds=None):
+        """spray_rt_domains_cell_surface: the boundary surfaces of the cells the
+        selects keep (see _surf_table) into slots (empty or loaded), extracted
+        and built on the device; normals, colours and bounds as in
+        tet_isosurface_domains."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(meshes) != n:
+            e = SprayRtError("cell_surface_domains: %d slots, %d meshes" % (n, len(meshes)))
+            e.code = -1
+            raise e
+        arr, sarr, carr, keep = _surf_table(meshes, selects)
+        m = max(n, 1)
+        sl = (C.c_int * m)(*slots)
+        out = self._bounds_out(bounds, n)
+        b, k = _addr(out)
+        nf = (C.c_size_t * m)()
+        self._check(lib().spray_rt_domains_cell_surface(
+            self.h, n, sl, arr, None if selects is None else sarr, carr, 1 if normals else 0, b,
+            nf), "domains_cell_surface")
+        for s in slots:
+            self._nverts.pop(s, None)  # the vertex count is the extraction's
+        if bounds is True:
+            self.sync()
+            return out[:n].cpu().numpy()
+        return out
+
+    def cell_surface_phase_times(self, on=None):
+        """spray_rt_cell_surface_phase_times of the last surface extraction, as
+        tet_phase_times (on switches the same sort timing)."""
+        if on is not None:
+            self._check(lib().spray_rt_tet_set_timing(self.h, 1 if on else 0), "tet_set_timing")
+        out = (C.c_double * 4)()
+        self._check(lib().spray_rt_cell_surface_phase_times(self.h, out),
+                    "cell_surface_phase_times")
         return list(out)
 
     def slot_export(self, slot, what):
