@@ -851,6 +851,16 @@ int spray_rt_occluded_scene_order(spray_rt_ctx_t ctx, const spray_rt_ray* rays,
 #define SPRAY_RT_RAYS_INCOHERENT 2
 int spray_rt_set_coherence(spray_rt_ctx_t ctx, int mode);
 
+/* What the launcher decided for the last scene launch (any of the
+ * spray_rt_*_scene* calls, frames included) of the process, not of ctx: not
+ * thread-safe, for tests that must prove which body of the scene kernel
+ * they ran.  out = { persist (1: persistent waves over the work queues, 0:
+ * one packet per wave), resident-block count of the launched kernel (0 while
+ * it was never computed), rays per dequeued chunk of its persistent form,
+ * W (64-domain words), stack entries, traversal (0 per lane, 1 packets,
+ * 2 adaptive), any hit, epilogue }.  All zero before the first launch. */
+int spray_rt_scene_launch_info(spray_rt_ctx_t ctx, int out[8]);
+
 /* ---- in-situ (domain-sharded, one rank per GPU) ---- */
 /* Domain -> rank map of the partition (InsituPartition::rank,
  * src/render/data_partition.h:48-56): owner[ndomains] host array, ranks in

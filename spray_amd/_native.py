@@ -155,6 +155,7 @@ SIGNATURES = {
     "spray_rt_gather_rows": (I, [P, P, SZ, P, SZ, P]),
     "spray_rt_exchange_plan": (I, [P, P, SZ, I, P, P]),
     "spray_rt_set_coherence": (I, [P, I]),
+    "spray_rt_scene_launch_info": (I, [P, P]),
     "spray_rt_spawn_shadows_ao": (I, [P, P, P, P, SZ, I, P, P, P]),
     "spray_rt_spawn_shadows_ao_ordered": (I, [P, P, P, P, SZ, I, P, P, P, P]),
     "spray_rt_spawn_shadows_ao_traced": (I, [P, P, P, P, SZ, I, P, P, P]),

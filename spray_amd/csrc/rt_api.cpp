@@ -1014,6 +1014,14 @@ int spray_rt_set_coherence(spray_rt_ctx_t c, int mode) {
   return SPRAY_RT_OK;
 }
 
+int spray_rt_scene_launch_info(spray_rt_ctx_t c, int out[8]) {
+  if (!c || !out) return SPRAY_RT_ERR_ARG;
+  const SceneLaunchInfo i = last_scene_launch();
+  const int v[8] = {i.persist, i.grid, i.chunk, i.W, i.STK, i.TRAV, i.ANY, i.EPI};
+  for (int k = 0; k < 8; ++k) out[k] = v[k];
+  return SPRAY_RT_OK;
+}
+
 int spray_rt_exchange_plan(spray_rt_ctx_t c, const uint64_t* rank_mask, size_t n,
                            int world, int64_t* idx, int64_t* starts) {
   if (!c) return SPRAY_RT_ERR_ARG;

@@ -42,6 +42,17 @@ struct SceneView {
   int coherence;    // SPRAY_RT_RAYS_* of the any-hit launches
 };
 
+// What the launcher decided for the last scene launch of the process (any
+// context, any stream): read-only, not thread-safe, for tests that must
+// prove which body of the scene kernel they ran.  grid is the launched
+// instantiation's resident-block count (0 while it was never computed),
+// chunk its SPRAY_CHUNK_CH / SPRAY_CHUNK_AH; the rest are its template
+// arguments.
+struct SceneLaunchInfo {
+  int persist, grid, chunk, W, STK, TRAV, ANY, EPI;
+};
+SceneLaunchInfo last_scene_launch();
+
 // counters (optional, device uint64[3]: nodes, tris, visits) select the
 // counting variant used to verify the canonical traversal.
 hipError_t launch_scene_intersect(hipStream_t s, const SceneView& v,

@@ -2204,6 +2204,11 @@ hipError_t launch_domains(hipStream_t s, const float* boxes, int ndom,
   return hipGetLastError();
 }
 
+// the last scene launch of the process (last_scene_launch(); not thread-safe)
+static SceneLaunchInfo g_last_scene = {};
+
+SceneLaunchInfo last_scene_launch() { return g_last_scene; }
+
 template <int W, bool ANY, bool COUNT, int EPI, int STK, int TRAV>
 static hipError_t launch_scene_t(hipStream_t s, SceneArgs a) {
   bool kPersist = ANY ? (SPRAY_PERSIST_AH != 0 || a.M >= kPersistAhRays) : SPRAY_PERSIST_CH != 0;
@@ -2226,6 +2231,8 @@ static hipError_t launch_scene_t(hipStream_t s, SceneArgs a) {
   // packet, against one block's walk here.
   if (kPersist && !a.d_count && (a.M + 63) / 64 <= size_t(grid) * (kBlock / 64)) kPersist = false;
   a.persist = kPersist ? 1 : 0;
+  g_last_scene = {a.persist, grid, int(ANY ? SPRAY_CHUNK_AH : SPRAY_CHUNK_CH), W, STK, TRAV,
+                  ANY ? 1 : 0, EPI};
   // the queue heads and the spawn count zeroed in one launch
   ClearSeg cs[2];
   int ncs = 0;

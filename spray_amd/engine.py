@@ -688,6 +688,15 @@ class RtContext:
         """Traversal form of the any-hit launches (results are identical)."""
         self._check(lib().spray_rt_set_coherence(self.h, int(mode)), "set_coherence")
 
+    def scene_launch_info(self):
+        """What the launcher decided for the last scene launch of the process
+        (not of this context; not thread-safe; for tests): dict(persist, grid,
+        chunk, W, STK, TRAV, ANY, EPI) -- spray_rt_scene_launch_info."""
+        out = (C.c_int * 8)()
+        self._check(lib().spray_rt_scene_launch_info(self.h, out), "scene_launch_info")
+        return dict(zip(("persist", "grid", "chunk", "W", "STK", "TRAV", "ANY", "EPI"),
+                        (int(x) for x in out)))
+
     # ---- domains ----
     def upload_domain(self, slot, verts, faces, colors=None, normals=None, async_=False):
         v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
