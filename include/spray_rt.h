@@ -703,6 +703,118 @@ int spray_rt_cell_surface_host(const spray_rt_cellmesh* mesh, const spray_rt_cel
  * spray_rt_tet_phase_times (the sort's device time while
  * spray_rt_tet_set_timing is on). */
 int spray_rt_cell_surface_phase_times(spray_rt_ctx_t ctx, double out_ms[4]);
+/* ---- clips of cell meshes by a level of their scalar field ---- */
+/* The surface of the part of a spray_rt_cellmesh on one side of values ==
+ * isovalue, as one indexed triangle mesh with a smooth cut face.  The rule is
+ * fixed, so that the kernels and the host restatement agree byte for byte
+ * (DESIGN.md section 17).
+ *
+ * Kept points: point p is kept when values[p] >= isovalue, with invert[i] != 0
+ * when it is not.  The solid is the kept side of the piecewise-linear
+ * interpolant over the tet split of spray_rt_cell_isosurface; its surface is a
+ * cap, the isosurface, and a skin, the part of the mesh's boundary on the kept
+ * side.
+ *
+ * Vertices come in two groups.  The first ncap_verts are exactly the vertices
+ * of spray_rt_cell_isosurface of the same mesh, byte for byte (positions,
+ * normals, colours), ascending by pair, whatever invert says; vert_pairs[v] =
+ * (a, b), a < b, the vertex's point pair, and vert_t[v] = (isovalue -
+ * values[a]) / (values[b] - values[a]).  Then come the kept points that some
+ * skin piece uses, ascending by point index: position and normal are the
+ * point's own bytes, the colour is map(g[p]) or color_rgb as for
+ * spray_rt_cell_surface, vert_pairs[v] = (p, p) and vert_t[v] = 0.  Another
+ * field h gathered as h[a] + t * (h[b] - h[a]) in float and mapped with
+ * spray_rt_colormap_apply recolours the slot through spray_rt_domains_recolor.
+ *
+ * Faces come in two groups.  The first ncap_faces are the faces of
+ * spray_rt_cell_isosurface, byte for byte, with corners 1 and 2 of each swapped
+ * where invert is set: Ng = (v0 - v1) x (v2 - v0) points out of the solid in
+ * both cases.  Then comes the skin.  A cell takes part when at least one of its
+ * listed points is kept; the skin's source is the triangles of
+ * spray_rt_cell_surface (SPRAY_RT_SELECT_ALL) over the cells that take part:
+ * face tables, keys, "occurs exactly once", the quad diagonal and the outward
+ * turn decided once per face are all that call's.  (A face that a cell without
+ * a kept point would have cancelled has no kept corner and gives nothing.)
+ * Each such triangle (v0, v1, v2), after the outward turn, is cut by the kept
+ * bits of its corners; with P_i the vertex of the kept point v_i, X(i,j) the
+ * cap vertex of the pair of corners i and j, and indices mod 3:
+ *   3 kept       (P_0, P_1, P_2)
+ *   0 kept       nothing
+ *   only k       (P_k, X(k,k+1), X(k,k+2))
+ *   all but k    (P_{k+1}, P_{k+2}, X(k+2,k)) then (P_{k+1}, X(k+2,k), X(k,k+1))
+ * Skin faces are ordered by cell in input order, then face in table order,
+ * then the triangle of a quad, then the piece.  Zero-area pieces are kept (a
+ * value equal to the isovalue gives t of 0 or 1); a cell that lists a point
+ * twice goes through the same rule.  Every edge of a boundary triangle is an
+ * edge of a tet of the split, so every X is one of the cap's welded vertices.
+ * No atomic and no hash decides an index: two runs give the same bytes.
+ *
+ * Normals: cap and skin share the vertices along the cut, so with point
+ * normals the shading normal there is the interpolated one on both sides;
+ * callers who want a crease along the cut pass with_normals = 0 (vnormals
+ * NULL).
+ *
+ * spray_rt_cell_clip has the argument shapes and NULL conventions of
+ * spray_rt_cell_surface, with invert (int32 [n], NULL: no mesh inverted),
+ * vert_pairs ([nverts][2] uint32) and vert_t ([nverts] float) beside them: any
+ * output or single entry may be NULL, all NULL only counts, a capacity (cap and
+ * skin together) that is too small gives SPRAY_RT_ERR_LIMIT with the four
+ * counts reported and no buffer written.  nverts_out / nfaces_out are the
+ * totals, ncap_verts_out / ncap_faces_out the cap's share of them.  Five host
+ * reads per call: spray_rt_cell_isosurface's three, the skin's status and
+ * face-instance totals, its vertex and piece counts.
+ *
+ * Errors, before anything is written and naming the mesh: every
+ * SPRAY_RT_ERR_ARG and SPRAY_RT_ERR_LIMIT of spray_rt_cell_isosurface and of
+ * spray_rt_cell_surface (npoints > 2^21 among them), checked for every cell
+ * whether it takes part or not; values is required.  A cut edge without a cap
+ * vertex cannot occur on input that passed these checks; the lookup is bounded
+ * all the same, never indexes with a miss, and reports SPRAY_RT_ERR_STATE. */
+int spray_rt_cell_clip(spray_rt_ctx_t ctx, int n, const spray_rt_cellmesh* meshes,
+                       const int32_t* invert, const spray_rt_grid_color* gcolors,
+                       float* const* verts, float* const* vnormals, uint32_t* const* colors,
+                       uint32_t* const* vert_pairs, float* const* vert_t, uint32_t* const* faces,
+                       const size_t* cap_verts, const size_t* cap_faces, size_t* nverts_out,
+                       size_t* nfaces_out, size_t* ncap_verts_out, size_t* ncap_faces_out);
+/* Meshes in, resident slots out, as spray_rt_domains_cell_surface: slots[i] is
+ * byte for byte a slot of spray_rt_domains_build of the clipped mesh.  At most
+ * seven host reads (the extraction's five and the build's two).  A failed call
+ * leaves every slot as it was; messages name the mesh and its slot.  Not for
+ * use while lanes run. */
+int spray_rt_domains_cell_clip(spray_rt_ctx_t ctx, int n, const int* slots,
+                               const spray_rt_cellmesh* meshes, const int32_t* invert,
+                               const spray_rt_grid_color* gcolors, int with_normals,
+                               float* d_bounds, size_t* nfaces_out);
+/* Host-only restatement (no GPU; every array is host memory): the arrays the
+ * kernels write, byte for byte.  gcolor may be NULL; any output may be NULL;
+ * vnormals_out needs point_normals. */
+int spray_rt_cell_clip_host(const spray_rt_cellmesh* mesh, int32_t invert,
+                            const spray_rt_grid_color* gcolor, size_t* nverts, size_t* nfaces,
+                            size_t* ncap_verts, size_t* ncap_faces, float* verts_out,
+                            float* vnormals_out, uint32_t* colors_out, uint32_t* vert_pairs_out,
+                            float* vert_t_out, uint32_t* faces_out);
+/* Where the last clip of the context spent its time.  out_ms[0..4] are
+ * spray_rt_cell_phase_times' boundaries for the cap: [0] wall clock from entry
+ * to the cell pass's host read, [1] from there to the tet count's read, [2] to
+ * the weld's read, [3] the enqueue of the cap's and the skin's emit passes,
+ * [4] the device time of the two sorts, the cap's pairs and the skin's faces
+ * (0 unless spray_rt_tet_set_timing is on).  out_ms[5] is the wall clock of
+ * the skin passes between the weld's read and the skin's second read: count,
+ * keys, sort, unique, skin count and both reads. */
+int spray_rt_cell_clip_phase_times(spray_rt_ctx_t ctx, double out_ms[6]);
+/* The signed distance field of a plane, scaled by the normal's length, as the
+ * values of a clip ("clip by a plane": spray_rt_cell_clip at isovalue 0 keeps
+ * the side the normal points to) or of an isosurface ("slice by a plane":
+ * spray_rt_cell_isosurface at isovalue 0):
+ *   values[p] = ((px - ox) * nx + (py - oy) * ny) + (pz - oz) * nz
+ * in float, term by term.  points ([npoints][3]) may be device or host memory;
+ * values_out is device memory.  SPRAY_RT_ERR_ARG for a non-finite origin or
+ * normal, a zero normal, or a NULL pointer with npoints > 0.  The host form
+ * writes host memory. */
+int spray_rt_plane_values(spray_rt_ctx_t ctx, const float* points, size_t npoints,
+                          const float origin[3], const float normal[3], float* values_out);
+int spray_rt_plane_values_host(const float* points, size_t npoints, const float origin[3],
+                               const float normal[3], float* values_out);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes

@@ -134,6 +134,12 @@ SIGNATURES = {
     "spray_rt_domains_cell_surface": (I, [P, I, P, P, P, P, I, P, P]),
     "spray_rt_cell_surface_host": (I, [P, P, P, P, P, P, P, P, P, P]),
     "spray_rt_cell_surface_phase_times": (I, [P, P]),
+    "spray_rt_cell_clip": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_cell_clip": (I, [P, I, P, P, P, P, I, P, P]),
+    "spray_rt_cell_clip_host": (I, [P, C.c_int32, P, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_cell_clip_phase_times": (I, [P, P]),
+    "spray_rt_plane_values": (I, [P, P, SZ, P, P, P]),
+    "spray_rt_plane_values_host": (I, [P, SZ, P, P, P]),
     "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
     "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),

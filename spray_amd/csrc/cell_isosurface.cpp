@@ -101,12 +101,12 @@ double ms_since(TetCall::Clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(TetCall::Clock::now() - t0).count();
 }
 
-std::string mesh_name(int i, const int* slots) {
+std::string mesh_name(const char* what, int i, const int* slots) {
   char buf[96];
   if (slots)
-    snprintf(buf, sizeof(buf), "%s (mesh %d, slot %d)", kWhat, i, slots[i]);
+    snprintf(buf, sizeof(buf), "%s (mesh %d, slot %d)", what, i, slots[i]);
   else
-    snprintf(buf, sizeof(buf), "%s (mesh %d)", kWhat, i);
+    snprintf(buf, sizeof(buf), "%s (mesh %d)", what, i);
   return std::string(buf);
 }
 
@@ -125,17 +125,17 @@ int cell_split(spray_rt_ctx* c, int n, const spray_rt_cellmesh* meshes,
                const std::vector<char>& want_normals, const TetCall& call, CellCall* out) {
   const size_t nj = size_t(n);
   if (n > 65535)
-    return fail(c, SPRAY_RT_ERR_LIMIT, "%s: more than 65535 meshes in one call", kWhat);
+    return fail(c, SPRAY_RT_ERR_LIMIT, "%s: more than 65535 meshes in one call", call.what);
   for (int i = 0; i < n; ++i) {
     int code;
     if (const char* why = mesh_error(meshes[i], &code))
-      return fail(c, code, "%s: %s", mesh_name(i, slots).c_str(), why);
+      return fail(c, code, "%s: %s", mesh_name(call.what, i, slots).c_str(), why);
     if (want_normals[size_t(i)] && !meshes[i].point_normals)
       return fail(c, SPRAY_RT_ERR_ARG, "%s: normals asked of a mesh without point_normals",
-                  mesh_name(i, slots).c_str());
+                  mesh_name(call.what, i, slots).c_str());
     float scale;
     if (const char* why = gcolors ? tet_color_error(&gcolors[i], &scale) : nullptr)
-      return fail(c, SPRAY_RT_ERR_ARG, "%s: %s", mesh_name(i, slots).c_str(), why);
+      return fail(c, SPRAY_RT_ERR_ARG, "%s: %s", mesh_name(call.what, i, slots).c_str(), why);
   }
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = stream_of(c);
@@ -219,10 +219,10 @@ int cell_split(spray_rt_ctx* c, int n, const spray_rt_cellmesh* meshes,
   const TetRec* h_rec = A.host(t_recs);
   for (int i = 0; i < n; ++i) {
     if (const char* why = status_error(h_status[i]))
-      return fail(c, SPRAY_RT_ERR_ARG, "%s: %s", mesh_name(i, slots).c_str(), why);
+      return fail(c, SPRAY_RT_ERR_ARG, "%s: %s", mesh_name(call.what, i, slots).c_str(), why);
     if (h_rec[i].ninst >= kMaxTets)
       return fail(c, SPRAY_RT_ERR_LIMIT, "%s: 2^29 or more tets from crossing cells",
-                  mesh_name(i, slots).c_str());
+                  mesh_name(call.what, i, slots).c_str());
   }
 
   // ---- the tets of the crossing cells, sized by the totals ----
@@ -259,15 +259,20 @@ int cell_split(spray_rt_ctx* c, int n, const spray_rt_cellmesh* meshes,
   return SPRAY_RT_OK;
 }
 
+}  // namespace
+
+namespace spray_rt {
+namespace detail {
+
 // The tet pipeline's first two stages on the split meshes.  A failure waits
 // for the stream: the pinned job table may still be on its way.
-int cell_weld(spray_rt_ctx* c, int n, const spray_rt_cellmesh* meshes,
+int cell_weld(spray_rt_ctx* c, const char* what, int n, const spray_rt_cellmesh* meshes,
               const spray_rt_grid_color* gcolors, const int* slots,
               const std::vector<char>& want_normals, TetCall* call) {
   CellCall cells;
+  call->what = what;
   int r = cell_split(c, n, meshes, gcolors, slots, want_normals, *call, &cells);
   if (r) return r;
-  call->what = kWhat;
   r = tet_count(c, n, cells.meshes.data(), cells.gcolors.empty() ? nullptr : cells.gcolors.data(),
                 slots, want_normals, call);
   if (!r) r = tet_weld(c, n, call);
@@ -276,7 +281,8 @@ int cell_weld(spray_rt_ctx* c, int n, const spray_rt_cellmesh* meshes,
   return r;
 }
 
-}  // namespace
+}  // namespace detail
+}  // namespace spray_rt
 
 extern "C" {
 
@@ -337,7 +343,7 @@ int spray_rt_cell_isosurface(spray_rt_ctx_t c, int n, const spray_rt_cellmesh* m
   std::vector<char> want_normals(size_t(n), 0);
   for (int i = 0; vnormals && i < n; ++i) want_normals[size_t(i)] = vnormals[i] != nullptr;
   TetCall call;
-  if (const int r = cell_weld(c, n, meshes, gcolors, nullptr, want_normals, &call)) return r;
+  if (const int r = cell_weld(c, kWhat, n, meshes, gcolors, nullptr, want_normals, &call)) return r;
   return tet_to_buffers(c, n, call, verts, vnormals, colors, faces, cap_verts, cap_faces,
                         nverts_out, nfaces_out);
 }
@@ -358,7 +364,7 @@ int spray_rt_domains_cell_isosurface(spray_rt_ctx_t c, int n, const int* slots,
     want_colors[k] = meshes[k].has_color || (gcolors && gcolors[k].field);
   }
   TetCall call;
-  if (const int r = cell_weld(c, n, meshes, gcolors, slots, want_normals, &call)) return r;
+  if (const int r = cell_weld(c, kWhat, n, meshes, gcolors, slots, want_normals, &call)) return r;
   return tet_to_slots(c, n, slots, call, want_normals, want_colors, d_bounds, nfaces_out);
 }
 

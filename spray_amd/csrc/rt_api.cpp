@@ -412,7 +412,8 @@ int spray_rt_destroy(spray_rt_ctx_t c) {
                   c->d_sah, c->d_sort, c->d_isomesh, c->d_tetinst, c->d_celltets, c->d_surfinst};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
-  for (JobArena* a : {&c->refit, &c->build, &c->iso, &c->recolor, &c->tet, &c->cell, &c->surf})
+  for (JobArena* a : {&c->refit, &c->build, &c->iso, &c->recolor, &c->tet, &c->cell, &c->surf,
+                      &c->clip})
     arena_release(a);
   if (c->recolor_copied) (void)hipEventDestroy(c->recolor_copied);
   for (hipEvent_t e : c->tet_ev)

@@ -109,6 +109,8 @@ struct spray_rt_ctx {
   void* d_surfinst = nullptr;       // cell surface: the per-face-instance scratch (keys, flags)
   size_t surfinst_cap = 0;
   double surf_ms[4] = {};  // spray_rt_cell_surface_phase_times, as tet_ms
+  spray_rt::detail::JobArena clip;  // cell clip: the skin's job tables, records | staged arrays, scratch
+  double clip_ms[6] = {};           // spray_rt_cell_clip_phase_times
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;

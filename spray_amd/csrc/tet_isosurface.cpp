@@ -387,8 +387,6 @@ int tet_weld(spray_rt_ctx* c, int n, TetCall* call) {
   return SPRAY_RT_OK;
 }
 
-namespace {
-
 // The vertex and face passes of a welded call into outs[n].
 int tet_emit(spray_rt_ctx* c, int n, const TetCall& call, const std::vector<TetOut>& outs) {
   hipStream_t s = stream_of(c);
@@ -404,8 +402,6 @@ int tet_emit(spray_rt_ctx* c, int n, const TetCall& call, const std::vector<TetO
   c->tet_ms[2] = ms_since(call.t0) - c->tet_ms[0] - c->tet_ms[1];
   return SPRAY_RT_OK;
 }
-
-}  // namespace
 
 int tet_to_buffers(spray_rt_ctx* c, int n, const TetCall& call, float* const* verts,
                    float* const* vnormals, uint32_t* const* colors, uint32_t* const* faces,

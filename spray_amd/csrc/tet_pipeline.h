@@ -47,6 +47,10 @@ int tet_count(spray_rt_ctx* c, int n, const spray_rt_tetmesh* meshes,
 // Keys, the sort and the run count of a counted call, then the vertex counts:
 // host read 2.
 int tet_weld(spray_rt_ctx* c, int n, TetCall* call);
+// The vertex and face passes of a welded call into outs[n].  The call's tables
+// and instance scratch (TetInst: sorted keys, block bases, in-block ids) stay
+// as they are until the next tet or cell extraction of the context.
+int tet_emit(spray_rt_ctx* c, int n, const TetCall& call, const std::vector<TetOut>& outs);
 // A welded call into the caller's buffers (spray_rt_tet_isosurface's arguments).
 int tet_to_buffers(spray_rt_ctx* c, int n, const TetCall& call, float* const* verts,
                    float* const* vnormals, uint32_t* const* colors, uint32_t* const* faces,
@@ -60,6 +64,12 @@ int tet_to_slots(spray_rt_ctx* c, int n, const int* slots, const TetCall& call,
                  float* d_bounds, size_t* nfaces_out);
 // What is wrong with the slot list of a call named what (0: nothing).
 int tet_slots_error(spray_rt_ctx* c, const char* what, int n, const int* slots);
+// cell_isosurface.cpp's extraction up to the tet pipeline's second host read,
+// for a call named what: the cell pass (host read 1), the split of the crossing
+// cells, tet_count and tet_weld on them.
+int cell_weld(spray_rt_ctx* c, const char* what, int n, const spray_rt_cellmesh* meshes,
+              const spray_rt_grid_color* gcolors, const int* slots,
+              const std::vector<char>& want_normals, TetCall* call);
 
 }  // namespace detail
 }  // namespace spray_rt

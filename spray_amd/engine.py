@@ -18,7 +18,8 @@ from ._native import (HIT_DTYPE, INVALID_ID, RAY_DTYPE, RTC_ISECT_DTYPE, BsdfRec
 __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_rays",
            "bvh_refit_host", "bvh_build_device_host", "isosurface_host",
            "isosurface_mapped_host", "colormap_host", "tet_isosurface_host",
-           "cell_isosurface_host", "cell_split_host", "cell_surface_host", "SLOT_COLORS",
+           "cell_isosurface_host", "cell_split_host", "cell_surface_host", "cell_clip_host",
+           "plane_values_host", "SLOT_COLORS",
            "SLOT_FACES",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
@@ -571,6 +572,71 @@ def cell_surface_host(points, types, offsets, conn, select=None, values=None, no
     call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, ids.ctypes.data,
          f.ctypes.data)
     return v, n, c, ids, f
+
+
+def _invert_arg(invert, n):
+    """invert (None, one flag, or one per mesh) -> int32 array of n or None."""
+    if invert is None:
+        return None
+    flags = [invert] * n if isinstance(invert, (bool, int)) else list(invert)
+    if len(flags) != n:
+        raise ValueError("cell_clip: one invert flag per mesh")
+    return (C.c_int32 * max(n, 1))(*[1 if f else 0 for f in flags])
+
+
+def cell_clip_host(points, types, offsets, conn, values, iso, invert=False, normals=None,
+                   cfield=None, cmap=None, color=None):
+    """spray_rt_cell_clip_host (no GPU): the surface of the part of a mesh of
+    mixed cells (see _cell_table; numpy arrays) with values >= iso (invert: the
+    other part) -> (verts float32 [nv, 3], normals float32 [nv, 3] or None
+    without point normals, colors uint32 [nv], vert_pairs uint32 [nv, 2], vert_t
+    float32 [nv], faces uint32 [nf, 3], ncap_verts, ncap_faces): the cap's
+    vertices and faces come first."""
+    m = dict(points=points, types=types, offsets=offsets, conn=conn, values=values, iso=iso,
+             normals=normals, cfield=cfield, cmap=cmap, color=color)
+    arr, carr, keep = _cell_table([m])
+    L = lib()
+    nv, nf, ncv, ncf = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_cell_clip_host(C.addressof(arr), 1 if invert else 0, C.addressof(carr),
+                                       C.byref(nv), C.byref(nf), C.byref(ncv), C.byref(ncf), *outs)
+        if rc != 0:
+            _cell_fail("cell_clip_host", rc)
+
+    call(None, None, None, None, None, None)
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals is not None else None
+    c = np.zeros(nv.value, np.uint32)
+    pairs = np.zeros((nv.value, 2), np.uint32)
+    t = np.zeros(nv.value, np.float32)
+    f = np.zeros((nf.value, 3), np.uint32)
+    call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, pairs.ctypes.data,
+         t.ctypes.data, f.ctypes.data)
+    return v, n, c, pairs, t, f, ncv.value, ncf.value
+
+
+def _plane_args(origin, normal):
+    o = np.ascontiguousarray(origin, np.float32).reshape(-1)
+    d = np.ascontiguousarray(normal, np.float32).reshape(-1)
+    if o.size != 3 or d.size != 3:
+        raise ValueError("plane_values: origin and normal have three components")
+    return o, d
+
+
+def plane_values_host(points, origin, normal):
+    """spray_rt_plane_values_host (no GPU): ((p - origin) . normal) of every
+    point, term by term in float32 -> float32 [npoints]."""
+    pts = np.ascontiguousarray(points, np.float32)
+    if pts.size % 3:
+        raise ValueError("plane_values: points are a [n, 3] array")
+    o, d = _plane_args(origin, normal)
+    out = np.zeros(pts.size // 3, np.float32)
+    rc = lib().spray_rt_plane_values_host(pts.ctypes.data, pts.size // 3, o.ctypes.data,
+                                          d.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        _cell_fail("plane_values_host", rc)
+    return out
 
 
 def host_parse_scene(desc, ply_path=""):
@@ -1244,6 +1310,118 @@ class RtContext:
         self._check(lib().spray_rt_cell_surface_phase_times(self.h, out),
                     "cell_surface_phase_times")
         return list(out)
+
+    # ---- clips of cell meshes ----
+    def cell_clip(self, meshes, invert=None, normals=True, capacity=None, count_only=False):
+        """spray_rt_cell_clip: the surfaces of the parts of meshes of mixed cells
+        (see _cell_table) with values >= iso (invert, one flag or one per mesh:
+        the other part) in one batched call -> [(verts float32 [nv, 3], normals
+        float32 [nv, 3] or None (normals False, or a mesh without them), colors
+        int32 [nv] holding the 0x00RRGGBB bits, vert_pairs int32 [nv, 2],
+        vert_t float32 [nv], faces int32 [nf, 3] holding the uint32 bits,
+        ncap_verts, ncap_faces)] as GPU tensors of the exact sizes (a counting
+        call first); the cap's vertices and faces come first.  capacity=(nverts,
+        nfaces) and count_only ([(nverts, nfaces, ncap_verts, ncap_faces)]) as
+        in tet_isosurface.  Enqueued on the context's stream."""
+        import torch
+        fn = lib().spray_rt_cell_clip
+        n = len(meshes)
+        arr, carr, keep = _cell_table(meshes)
+        inv = _invert_arg(invert, n)
+        m = max(n, 1)
+        nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        ncv, ncf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        if capacity is None or count_only:
+            self._check(fn(self.h, n, arr, inv, carr, None, None, None, None, None, None, None,
+                           None, nv, nf, ncv, ncf), "cell_clip")
+            caps = [(nv[i], nf[i]) for i in range(n)]
+            if count_only:
+                return [(nv[i], nf[i], ncv[i], ncf[i]) for i in range(n)]
+        else:
+            caps = [(int(capacity[0]), int(capacity[1]))] * n
+        dev = "cuda:%d" % self._device
+        # zeroed, one element at least: a buffer a failed call must not touch
+        v = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) for cv, _ in caps]
+        nr = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev)
+              if normals and meshes[i].get("normals") is not None else None
+              for i, (cv, _) in enumerate(caps)]
+        col = [torch.zeros(max(cv, 1), dtype=torch.int32, device=dev) for cv, _ in caps]
+        pairs = [torch.zeros((max(cv, 1), 2), dtype=torch.int32, device=dev) for cv, _ in caps]
+        vt = [torch.zeros(max(cv, 1), dtype=torch.float32, device=dev) for cv, _ in caps]
+        f = [torch.zeros((max(cf, 1), 3), dtype=torch.int32, device=dev) for _, cf in caps]
+
+        def ptrs(xs):
+            if all(x is None for x in xs):
+                return None
+            return (C.c_void_p * m)(*[None if x is None else x.data_ptr() for x in xs])
+
+        _fills_done()
+        try:
+            self._check(fn(
+                self.h, n, arr, inv, carr, ptrs(v), ptrs(nr), ptrs(col), ptrs(pairs), ptrs(vt),
+                ptrs(f), (C.c_size_t * m)(*[c[0] for c in caps]),
+                (C.c_size_t * m)(*[c[1] for c in caps]), nv, nf, ncv, ncf), "cell_clip")
+        except SprayRtError as e:
+            e.counts = [(nv[i], nf[i], ncv[i], ncf[i]) for i in range(n)]
+            e.buffers = (v, [x for x in nr if x is not None], col, pairs, vt, f)
+            raise
+        cut = lambda x, k: None if x is None else x[:k]
+        return [(v[i][:nv[i]], cut(nr[i], nv[i]), col[i][:nv[i]], pairs[i][:nv[i]],
+                 vt[i][:nv[i]], f[i][:nf[i]], ncv[i], ncf[i]) for i in range(n)]
+
+    def cell_clip_domains(self, slots, meshes, invert=None, normals=True, bounds=None):
+        """spray_rt_domains_cell_clip: the clipped meshes (see cell_clip) into
+        slots (empty or loaded), extracted and built on the device; normals,
+        colours and bounds as in tet_isosurface_domains."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(meshes) != n:
+            e = SprayRtError("cell_clip_domains: %d slots, %d meshes" % (n, len(meshes)))
+            e.code = -1
+            raise e
+        arr, carr, keep = _cell_table(meshes)
+        inv = _invert_arg(invert, n)
+        m = max(n, 1)
+        sl = (C.c_int * m)(*slots)
+        out = self._bounds_out(bounds, n)
+        b, k = _addr(out)
+        nf = (C.c_size_t * m)()
+        self._check(lib().spray_rt_domains_cell_clip(
+            self.h, n, sl, arr, inv, carr, 1 if normals else 0, b, nf), "domains_cell_clip")
+        for s in slots:
+            self._nverts.pop(s, None)  # the vertex count is the extraction's
+        if bounds is True:
+            self.sync()
+            return out[:n].cpu().numpy()
+        return out
+
+    def cell_clip_phase_times(self, on=None):
+        """spray_rt_cell_clip_phase_times of the last clip -> cell_phase_times'
+        five for the cap ([3] the emit of cap and skin, [4] both sorts), then
+        the wall clock of the skin passes; on switches the sorts' timing."""
+        if on is not None:
+            self._check(lib().spray_rt_tet_set_timing(self.h, 1 if on else 0), "tet_set_timing")
+        out = (C.c_double * 6)()
+        self._check(lib().spray_rt_cell_clip_phase_times(self.h, out), "cell_clip_phase_times")
+        return list(out)
+
+    def plane_values(self, points, origin, normal, out=None):
+        """spray_rt_plane_values: ((p - origin) . normal) of every point (float32
+        [n, 3], numpy or a GPU tensor) -> float32 GPU tensor [n] (out, if given:
+        a float32 GPU tensor of that many elements), the values of a plane clip
+        or slice at isovalue 0.  Enqueued on the context's stream."""
+        import torch
+        pts, npts = _tet_array(points, np.float32, 3, "points")
+        o, d = _plane_args(origin, normal)
+        if out is None:
+            out = torch.zeros(npts, dtype=torch.float32, device="cuda:%d" % self._device)
+            _fills_done()
+        elif out.numel() != npts or out.dtype != torch.float32:
+            raise ValueError("plane_values: out holds one float32 per point")
+        a, k = _addr(pts)
+        self._check(lib().spray_rt_plane_values(self.h, a, npts, o.ctypes.data, d.ctypes.data,
+                                                out.data_ptr()), "plane_values")
+        return out
 
     def slot_export(self, slot, what):
         """One array of a resident slot as numpy: SLOT_NODES / SLOT_QNODES4 as
