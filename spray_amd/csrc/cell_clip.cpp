@@ -470,7 +470,7 @@ int clip_count(spray_rt_ctx* c, int n, const spray_rt_cellmesh* meshes, const in
     c->clip_ms[4] += double(sort_ms);
   }
   for (int i = 0; i < n; ++i)
-    if (h_status[i] & clip::kMiss)
+    if (h_status[i] & clip::kMiss)  // a guard no known input reaches: see clip_common.h
       return fail(c, SPRAY_RT_ERR_STATE, "%s: a cut edge of the skin has no cap vertex",
                   mesh_name(i, slots).c_str());
   call->nsv.resize(nj);

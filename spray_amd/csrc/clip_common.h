@@ -27,7 +27,13 @@ namespace spray_rt {
 namespace clip {
 
 // status bit of one mesh of a call, above surf_common.h's: a cut edge of the
-// skin whose pair is not among the cap's (never on input that passed the checks)
+// skin whose pair is not among the cap's (never on input that passed the checks).
+// A guard, not a reachable error: a cut edge of a boundary triangle is an edge
+// of the cell's own tet split, which cuts a quad by the same smallest-index
+// rule.  tests/test_mesh_cases.py::test_collapsed_family_clips_and_surfaces
+// clips every single-position collapse of each cell type on the host (which
+// raises on any status) and tests/test_gpu_mesh_cases.py::test_many_segments
+// the same family on the device; none sets it.
 constexpr uint32_t kMiss = 512;
 
 SPRAY_HD bool kept(float f, float isovalue, uint32_t invert) {
