@@ -815,6 +815,150 @@ int spray_rt_plane_values(spray_rt_ctx_t ctx, const float* points, size_t npoint
                           const float origin[3], const float normal[3], float* values_out);
 int spray_rt_plane_values_host(const float* points, size_t npoints, const float origin[3],
                                const float normal[3], float* values_out);
+/* ---- streamlines of vector grids, as polylines and as tubes ---- */
+#define SPRAY_RT_STREAM_FORWARD 0
+#define SPRAY_RT_STREAM_BACKWARD 1
+#define SPRAY_RT_STREAM_BOTH 2
+#define SPRAY_RT_LINE_END_GRID 0  /* a stage point or the new point left the grid (or was not finite) */
+#define SPRAY_RT_LINE_END_STEPS 1 /* max_steps taken */
+#define SPRAY_RT_LINE_END_SPEED 2 /* speed unusable at the point, or the step moved nothing */
+#define SPRAY_RT_LINE_END_SEED 3  /* the seed is outside the grid: the line has no points */
+/* One structured grid of vectors, the seeds to trace from and how. */
+typedef struct spray_rt_vecfield {
+  const float* vectors; /* [nz][ny][nx][3], x fastest; device or host memory */
+  int32_t dims[3];      /* as spray_rt_grid */
+  float origin[3];
+  float spacing[3];
+  const float* seeds;   /* [nseeds][3] world positions; device or host memory */
+  size_t nseeds;
+  float step;           /* > 0, time units: fixed-step classical RK4 of dx/dt = v(x) */
+  int32_t max_steps;    /* 0 .. 65535 per direction */
+  int32_t direction;    /* SPRAY_RT_STREAM_* */
+  float min_speed;      /* > 0, min_speed * min_speed a normal float */
+} spray_rt_vecfield;
+/* The tube drawn round every line of a field. */
+typedef struct spray_rt_tube {
+  float radius;         /* > 0, finite */
+  int32_t nsides;       /* 3 .. 16 */
+  uint32_t color_rgb;   /* one colour for every vertex ... */
+  int32_t has_color;    /* ... or none (spray_rt_domains_stream_tubes only) */
+} spray_rt_tube;
+/* The rule is fixed, so that the kernels and the host restatement agree byte
+ * for byte: float, no contraction, division and square
+ * root correctly rounded; lerp(a, b, t) = a + t * (b - a).
+ *
+ * Sample v(p).  Per axis g = (p - origin) / spacing; p is inside when g >= 0 &&
+ * g <= float(n - 1) on all three axes (a NaN fails).  i = min(int(floorf(g)),
+ * n - 2), f = g - float(i): a point on the upper face uses the last cell with
+ * f == 1.  The trilinear value per component: the four x-lerps of the cell's
+ * corner pairs (in the order y0z0, y1z0, y0z1, y1z1), the two y-lerps, the
+ * z-lerp.
+ *
+ * Step.  h = +step forward, -step backward, hh = 0.5f * h, h6 = h / 6.0f;
+ * k1 = v(p); q2 = p + hh * k1, k2 = v(q2); q3 = p + hh * k2, k3 = v(q3);
+ * q4 = p + h * k3, k4 = v(q4); p' = p + h6 * (((k1 + 2 * k2) + 2 * k3) + k4).
+ * The speed at p is usable when msq <= d < inf, d = (k1x * k1x + k1y * k1y) +
+ * k1z * k1z, msq = min_speed * min_speed.  The step is taken when the speed is
+ * usable, q2, q3, q4 and p' are inside, p' differs from p in some bit and
+ * fewer than max_steps steps have been taken; otherwise the half-line ends at
+ * p, with the first reason that applies of SPEED, GRID, SPEED (no motion),
+ * STEPS, in that order.
+ *
+ * Lines.  Seed s of a field gives line s: the backward half's points in reverse
+ * order, the seed, the forward half's points.  A seed outside the grid gives an
+ * empty line with both end reasons SEED; a half the direction leaves out has
+ * no points and the end reason STEPS.  line_offsets[s] is the line's first
+ * point, line_offsets[nseeds] the number of points; line_info[s] = {nback,
+ * end_back | end_fwd << 8}, nback the points in front of the seed.
+ *
+ * Tangent and frame.  T = k1 / sqrtf(d) per component at a point whose speed
+ * is usable, else the tangent of the neighbouring point nearer the seed.  At
+ * the seed N is the normalised e - T_a * T, e the unit vector of the axis a
+ * with the smallest |T_a| (the lowest axis on a tie); along each half
+ * w = N_prev - dot(N_prev, T) * T, and N is the normalised w if dot(w, w) >=
+ * 0.25f, else the axis rule again.  dot(a, b) = (ax * bx + ay * by) + az * bz,
+ * normalised x = x / sqrtf(dot(x, x)) per component, B = T x N (each
+ * component a difference of two products).
+ *
+ * Tube.  A line of m >= 2 points gives m * nsides + 2 vertices and 2 * nsides *
+ * m faces, lines of fewer points nothing.  Ring vertex k of point j is vertex
+ * j * nsides + k: off = c_k * N + s_k * B per component, position p_j + radius *
+ * off, normal off, colour map(g(p_j)) with the colour field g sampled like v
+ * (spray_rt_grid_color), else color_rgb; (c_k, s_k) = spray_rt_tube_ring_host.
+ * Then the cap centres m * nsides (p_first, normal -T) and m * nsides + 1
+ * (p_last, normal +T).  Faces: for segment j and side k, with a = (j, k), b =
+ * (j, k + 1 mod nsides), c = (j + 1, k), d = (j + 1, k + 1 mod nsides), the
+ * triangles (a, c, b) and (b, c, d); then the first cap's fan (centre, (0, k),
+ * (0, k + 1)) for every k, then the last cap's (centre, (m - 1, k + 1), (m - 1,
+ * k)): Ng = (v0 - v1) x (v2 - v0) points away from the tube.  Vertex numbers
+ * count through a field: output order is line, point, side.  No atomic decides
+ * an index, two runs give the same bytes.
+ *
+ * spray_rt_streamlines traces n fields in one batched call on the context's
+ * stream into the caller's device buffers: points[i] float [cap_points[i]][3],
+ * line_offsets[i] uint32 [nseeds + 1], line_info[i] uint32 [nseeds][2]; any of
+ * the arrays, or single entries, may be NULL.  npoints_out (host, optional) is
+ * written on return: the call's one host read.  points == NULL only counts.  A
+ * capacity that is too small gives SPRAY_RT_ERR_LIMIT with the counts reported
+ * and nothing written.
+ *
+ * Errors, before anything is written, naming the field: SPRAY_RT_ERR_ARG for a
+ * NULL pointer with a nonzero count, dims < 2, a bad spacing, origin, step,
+ * min_speed, radius, nsides or direction, max_steps out of range, a non-finite
+ * seed coordinate, vector sample or colour sample (found by a check pass,
+ * reported at the host read), the colour map errors of
+ * spray_rt_isosurface_mapped; SPRAY_RT_ERR_LIMIT for 2^31 or more points in a
+ * grid, 2^31 or more seeds, 2^32 or more points of lines, 2^32 or more
+ * vertices, 2^29 or more faces. */
+int spray_rt_streamlines(spray_rt_ctx_t ctx, int n, const spray_rt_vecfield* fields,
+                         float* const* points, uint32_t* const* line_offsets,
+                         uint32_t* const* line_info, const size_t* cap_points,
+                         size_t* npoints_out);
+/* The tubes of n fields into the caller's device buffers, with the conventions
+ * of spray_rt_isosurface_mapped: verts / vnormals / colors / faces, or single
+ * entries, may be NULL independently, all NULL only counts; gcolors (optional)
+ * is an array of colour maps over the fields' dims, a field without one takes
+ * color_rgb.  One host read. */
+int spray_rt_stream_tubes(spray_rt_ctx_t ctx, int n, const spray_rt_vecfield* fields,
+                          const spray_rt_tube* tubes, const spray_rt_grid_color* gcolors,
+                          float* const* verts, float* const* vnormals, uint32_t* const* colors,
+                          uint32_t* const* faces, const size_t* cap_verts, const size_t* cap_faces,
+                          size_t* nverts_out, size_t* nfaces_out);
+/* Fields in, resident slots out: afterwards slots[i] is a slot of
+ * spray_rt_domains_build of the tube mesh of fields[i] (with its normals if
+ * with_normals, its colours if it has a colour field or has_color), byte for
+ * byte.  d_bounds and nfaces_out as in spray_rt_domains_isosurface.  At most
+ * three host reads (the counts, and the build's two).  A failed call leaves
+ * every slot as it was; the errors above, a bad slot or a slot listed twice
+ * (SPRAY_RT_ERR_ARG), and the build's.  spray_rt_last_error names the field and
+ * the slot.  A field without tubes gives the empty slot an empty upload gives.
+ * Not for use while lanes run. */
+int spray_rt_domains_stream_tubes(spray_rt_ctx_t ctx, int n, const int* slots,
+                                  const spray_rt_vecfield* fields, const spray_rt_tube* tubes,
+                                  const spray_rt_grid_color* gcolors, int with_normals,
+                                  float* d_bounds, size_t* nfaces_out);
+/* Host-only restatements (no GPU; the arrays are host memory): the arrays the
+ * kernels write, byte for byte.  The sizes are always reported; any output may
+ * be NULL (points_out float[*npoints][3], line_offsets_out uint32[nseeds + 1],
+ * line_info_out uint32[nseeds][2]; verts_out / vnormals_out float[*nverts][3],
+ * colors_out uint32[*nverts], faces_out uint32[*nfaces][3]).  gcolor may be
+ * NULL. */
+int spray_rt_streamlines_host(const spray_rt_vecfield* field, size_t* npoints, float* points_out,
+                              uint32_t* line_offsets_out, uint32_t* line_info_out);
+int spray_rt_stream_tubes_host(const spray_rt_vecfield* field, const spray_rt_tube* tube,
+                               const spray_rt_grid_color* gcolor, size_t* nverts, size_t* nfaces,
+                               float* verts_out, float* vnormals_out, uint32_t* colors_out,
+                               uint32_t* faces_out);
+/* The cross-section table the tubes use: out[k] = {(float)cos(a), (float)sin(a)},
+ * a = (6.283185307179586 * k) / nsides evaluated in double, k < nsides (3 ..
+ * 16): exposed so that a restatement need not reproduce libm. */
+int spray_rt_tube_ring_host(int32_t nsides, float out[][2]);
+/* Wall-clock milliseconds of the last streamline call of the context:
+ * out_ms[0] to the end of the host read (staging, the check pass, the count
+ * pass: the first integration), [1] the second integration and the expansion
+ * (their enqueue; completed where an array was staged from the host), [2] the
+ * device build of the domains form (its two host reads wait for [1]'s work). */
+int spray_rt_stream_phase_times(spray_rt_ctx_t ctx, double out_ms[3]);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes

@@ -88,6 +88,23 @@ class CellSelect(C.Structure):
 
 assert C.sizeof(CellSelect) == 24
 
+
+class VecField(C.Structure):
+    """spray_rt_vecfield."""
+    _fields_ = [("vectors", C.c_void_p), ("dims", C.c_int32 * 3), ("origin", C.c_float * 3),
+                ("spacing", C.c_float * 3), ("seeds", C.c_void_p), ("nseeds", C.c_size_t),
+                ("step", C.c_float), ("max_steps", C.c_int32), ("direction", C.c_int32),
+                ("min_speed", C.c_float)]
+
+
+class Tube(C.Structure):
+    """spray_rt_tube."""
+    _fields_ = [("radius", C.c_float), ("nsides", C.c_int32), ("color_rgb", C.c_uint32),
+                ("has_color", C.c_int32)]
+
+
+assert C.sizeof(VecField) == 80 and C.sizeof(Tube) == 16
+
 # every symbol the public headers declare: (restype, argtypes)
 P = C.c_void_p
 SZ = C.c_size_t
@@ -140,6 +157,13 @@ SIGNATURES = {
     "spray_rt_cell_clip_phase_times": (I, [P, P]),
     "spray_rt_plane_values": (I, [P, P, SZ, P, P, P]),
     "spray_rt_plane_values_host": (I, [P, SZ, P, P, P]),
+    "spray_rt_streamlines": (I, [P, I, P, P, P, P, P, P]),
+    "spray_rt_stream_tubes": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_stream_tubes": (I, [P, I, P, P, P, P, I, P, P]),
+    "spray_rt_streamlines_host": (I, [P, P, P, P, P]),
+    "spray_rt_stream_tubes_host": (I, [P, P, P, P, P, P, P, P, P]),
+    "spray_rt_tube_ring_host": (I, [C.c_int32, P]),
+    "spray_rt_stream_phase_times": (I, [P, P]),
     "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
     "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),

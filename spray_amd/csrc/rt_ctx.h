@@ -111,6 +111,8 @@ struct spray_rt_ctx {
   double surf_ms[4] = {};  // spray_rt_cell_surface_phase_times, as tet_ms
   spray_rt::detail::JobArena clip;  // cell clip: the skin's job tables, records | staged arrays, scratch
   double clip_ms[6] = {};           // spray_rt_cell_clip_phase_times
+  spray_rt::detail::JobArena stream;  // streamlines: job tables, records | staged arrays, per-lane scratch
+  double stream_ms[3] = {};           // spray_rt_stream_phase_times
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;

@@ -19,7 +19,9 @@ __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_r
            "bvh_refit_host", "bvh_build_device_host", "isosurface_host",
            "isosurface_mapped_host", "colormap_host", "tet_isosurface_host",
            "cell_isosurface_host", "cell_split_host", "cell_surface_host", "cell_clip_host",
-           "plane_values_host", "SLOT_COLORS",
+           "plane_values_host", "streamlines_host", "stream_tubes_host", "tube_ring",
+           "STREAM_FORWARD", "STREAM_BACKWARD", "STREAM_BOTH", "LINE_END_GRID", "LINE_END_STEPS",
+           "LINE_END_SPEED", "LINE_END_SEED", "SLOT_COLORS",
            "SLOT_FACES",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
@@ -636,6 +638,158 @@ def plane_values_host(points, origin, normal):
                                           d.ctypes.data, out.ctypes.data)
     if rc != 0:
         _cell_fail("plane_values_host", rc)
+    return out
+
+
+STREAM_FORWARD, STREAM_BACKWARD, STREAM_BOTH = 0, 1, 2
+LINE_END_GRID, LINE_END_STEPS, LINE_END_SPEED, LINE_END_SEED = 0, 1, 2, 3
+
+
+def _float_array(x, what, tail):
+    """A float32 numpy array or GPU tensor whose shape ends in tail."""
+    if hasattr(x, "data_ptr"):
+        if x.element_size() != 4 or not x.is_floating_point():
+            raise TypeError("streamlines: %s are float32" % what)
+    else:
+        x = np.ascontiguousarray(x, np.float32)
+    if tuple(x.shape[len(x.shape) - len(tail):]) != tuple(tail):
+        raise ValueError("streamlines: %s are a [..., %s] array"
+                         % (what, ", ".join(str(t) for t in tail)))
+    return x
+
+
+def _stream_tables(fields, tubes=None):
+    """Dicts with the keys vectors (float32 [nz, ny, nx, 3]), origin, spacing,
+    seeds (float32 [nseeds, 3]), step, max_steps and optionally direction
+    (STREAM_FORWARD), min_speed (1e-6), cfield (float32 [nz, ny, nx]) and cmap =
+    (table uint32[n], lo, hi); arrays are numpy arrays or torch tensors on the
+    GPU.  tubes: dicts with radius, nsides and optionally color, one per field
+    or one for all -> (spray_rt_vecfield array, spray_rt_tube array or None,
+    spray_rt_grid_color array, keepalive)."""
+    from ._native import Tube, VecField
+    m = max(len(fields), 1)
+    arr, carr = (VecField * m)(), (_GridColor * m)()
+    keep = []
+    for f, rec, crec in zip(fields, arr, carr):
+        vec = _float_array(f["vectors"], "vectors", (3,))
+        if len(vec.shape) != 4:
+            raise ValueError("streamlines: vectors are a [nz, ny, nx, 3] array")
+        seeds = _float_array(f["seeds"], "seeds", (3,))
+        nseeds = int(np.prod(seeds.shape[:-1])) if len(seeds.shape) > 1 else 1
+        keep += [vec, seeds]
+        rec.vectors = _addr(vec)[0]
+        nz, ny, nx = (int(d) for d in vec.shape[:3])
+        rec.dims = (C.c_int32 * 3)(nx, ny, nz)
+        rec.origin = (C.c_float * 3)(*[float(x) for x in f["origin"]])
+        rec.spacing = (C.c_float * 3)(*[float(x) for x in f["spacing"]])
+        rec.seeds = _addr(seeds)[0] if nseeds else None
+        rec.nseeds = nseeds
+        rec.step = float(f["step"])
+        rec.max_steps = int(f["max_steps"])
+        rec.direction = int(f.get("direction", STREAM_FORWARD))
+        rec.min_speed = float(f.get("min_speed", 1e-6))
+        cf = f.get("cfield")
+        if cf is not None:
+            cf = _float_array(cf, "colour fields", ())
+            if tuple(cf.shape) != tuple(vec.shape[:3]):
+                raise ValueError("streamlines: a colour field has its grid's shape")
+            keep.append(cf)
+            crec.field = _addr(cf)[0]
+            if f.get("cmap") is not None:
+                t, crec.table_rgb, crec.ntable, crec.lo, crec.hi = _cmap_args(f["cmap"])
+                keep.append(t)
+    tarr = None
+    if tubes is not None:
+        if isinstance(tubes, dict):
+            tubes = [tubes] * len(fields)
+        if len(tubes) != len(fields):
+            raise ValueError("stream_tubes: one tube per field")
+        tarr = (Tube * m)()
+        for t, rec in zip(tubes, tarr):
+            rec.radius = float(t["radius"])
+            rec.nsides = int(t["nsides"])
+            color = t.get("color")
+            rec.has_color = 0 if color is None else 1
+            rec.color_rgb = 0 if color is None else int(color)
+    return arr, tarr, carr, keep
+
+
+def _stream_field(vectors, origin, spacing, seeds, step, max_steps, direction, min_speed,
+                  cfield=None, cmap=None):
+    return dict(vectors=np.ascontiguousarray(vectors, np.float32), origin=origin, spacing=spacing,
+                seeds=np.ascontiguousarray(seeds, np.float32).reshape(-1, 3), step=step,
+                max_steps=max_steps, direction=direction, min_speed=min_speed, cfield=cfield,
+                cmap=cmap)
+
+
+def streamlines_host(vectors, origin, spacing, seeds, step, max_steps,
+                     direction=STREAM_FORWARD, min_speed=1e-6):
+    """spray_rt_streamlines_host (no GPU): the polylines RtContext.streamlines
+    traces -> (points float32 [np, 3], line_offsets uint32 [nseeds + 1],
+    line_info uint32 [nseeds, 2])."""
+    f = _stream_field(vectors, origin, spacing, seeds, step, max_steps, direction, min_speed)
+    arr, _, _, keep = _stream_tables([f])
+    L = lib()
+    npts = C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_streamlines_host(C.addressof(arr), C.byref(npts), *outs)
+        if rc != 0:
+            e = SprayRtError("streamlines_host failed (%d)" % rc)
+            e.code = rc
+            e.counts = npts.value
+            raise e
+
+    call(None, None, None)
+    ns = int(arr[0].nseeds)
+    p = np.zeros((npts.value, 3), np.float32)
+    off = np.zeros(ns + 1, np.uint32)
+    info = np.zeros((ns, 2), np.uint32)
+    call(p.ctypes.data, off.ctypes.data, info.ctypes.data)
+    return p, off, info
+
+
+def stream_tubes_host(vectors, origin, spacing, seeds, step, max_steps, radius, nsides,
+                      direction=STREAM_FORWARD, min_speed=1e-6, color=None, cfield=None, cmap=None,
+                      normals=True, count_only=False):
+    """spray_rt_stream_tubes_host (no GPU): the tube mesh RtContext.stream_tubes
+    builds -> (verts float32 [nv, 3], normals float32 [nv, 3] or None, colors
+    uint32 [nv], faces uint32 [nf, 3]); count_only: (nv, nf)."""
+    f = _stream_field(vectors, origin, spacing, seeds, step, max_steps, direction, min_speed,
+                      cfield, cmap)
+    arr, tarr, carr, keep = _stream_tables([f], dict(radius=radius, nsides=nsides, color=color))
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_stream_tubes_host(C.addressof(arr), C.addressof(tarr), C.addressof(carr),
+                                          C.byref(nv), C.byref(nf), *outs)
+        if rc != 0:
+            e = SprayRtError("stream_tubes_host failed (%d)" % rc)
+            e.code = rc
+            e.counts = (nv.value, nf.value)
+            raise e
+
+    call(None, None, None, None)
+    if count_only:
+        return nv.value, nf.value
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals else None
+    c = np.zeros(nv.value, np.uint32)
+    fc = np.zeros((nf.value, 3), np.uint32)
+    call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, fc.ctypes.data)
+    return v, n, c, fc
+
+
+def tube_ring(nsides):
+    """spray_rt_tube_ring_host: the tubes' cross-section table -> float32
+    [nsides, 2] of (cos, sin)."""
+    out = np.zeros((max(int(nsides), 0), 2), np.float32)
+    rc = lib().spray_rt_tube_ring_host(int(nsides), out.ctypes.data)
+    if rc != 0:
+        e = SprayRtError("tube_ring failed (%d)" % rc)
+        e.code = rc
+        raise e
     return out
 
 
@@ -1422,6 +1576,120 @@ class RtContext:
         self._check(lib().spray_rt_plane_values(self.h, a, npts, o.ctypes.data, d.ctypes.data,
                                                 out.data_ptr()), "plane_values")
         return out
+
+    # ---- streamlines ----
+    def streamlines(self, fields, capacity=None, count_only=False):
+        """spray_rt_streamlines: the streamlines of vector grids (see
+        _stream_tables) in one batched call -> [(points float32 [np, 3],
+        line_offsets int32 [nseeds + 1], line_info int32 [nseeds, 2], holding
+        the uint32 bits)] as GPU tensors of the exact sizes (a counting call
+        first).  capacity skips the counting call and traces into buffers of
+        that many points per field (SPRAY_RT_ERR_LIMIT if one is too small);
+        count_only: the point counts alone."""
+        import torch
+        n = len(fields)
+        arr, _, _, keep = _stream_tables(fields)
+        m = max(n, 1)
+        npts = (C.c_size_t * m)()
+        fn = lib().spray_rt_streamlines
+        if capacity is None or count_only:
+            self._check(fn(self.h, n, arr, None, None, None, None, npts), "streamlines")
+            if count_only:
+                return [npts[i] for i in range(n)]
+            caps = [npts[i] for i in range(n)]
+        else:
+            caps = [int(capacity)] * n
+        dev = "cuda:%d" % self._device
+        # zeroed, one element at least: a buffer a failed call must not touch
+        p = [torch.zeros((max(c, 1), 3), dtype=torch.float32, device=dev) for c in caps]
+        off = [torch.zeros(int(arr[i].nseeds) + 1, dtype=torch.int32, device=dev)
+               for i in range(n)]
+        info = [torch.zeros((max(int(arr[i].nseeds), 1), 2), dtype=torch.int32, device=dev)
+                for i in range(n)]
+        ptrs = lambda xs: (C.c_void_p * m)(*[x.data_ptr() for x in xs])
+        _fills_done()
+        try:
+            self._check(fn(self.h, n, arr, ptrs(p), ptrs(off), ptrs(info),
+                           (C.c_size_t * m)(*caps), npts), "streamlines")
+        except SprayRtError as e:
+            e.counts = [npts[i] for i in range(n)]
+            e.buffers = (p, off, info)
+            raise
+        return [(p[i][:npts[i]], off[i], info[i][:int(arr[i].nseeds)]) for i in range(n)]
+
+    def stream_tubes(self, fields, tubes, normals=True, capacity=None, count_only=False):
+        """spray_rt_stream_tubes: the streamlines of fields as tubes (see
+        _stream_tables) -> [(verts float32 [nv, 3], normals float32 [nv, 3] or
+        None, colors int32 [nv] holding the 0x00RRGGBB bits, faces int32 [nf, 3]
+        holding the uint32 bits)] as GPU tensors.  capacity=(nverts, nfaces) and
+        count_only as in streamlines (count_only: [(nv, nf)])."""
+        import torch
+        n = len(fields)
+        arr, tarr, carr, keep = _stream_tables(fields, tubes)
+        m = max(n, 1)
+        nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        fn = lib().spray_rt_stream_tubes
+        if capacity is None or count_only:
+            self._check(fn(self.h, n, arr, tarr, carr, None, None, None, None, None, None, nv, nf),
+                        "stream_tubes")
+            if count_only:
+                return [(nv[i], nf[i]) for i in range(n)]
+            caps = [(nv[i], nf[i]) for i in range(n)]
+        else:
+            caps = [(int(capacity[0]), int(capacity[1]))] * n
+        dev = "cuda:%d" % self._device
+        # zeroed, one element at least: a buffer a failed call must not touch
+        v = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) for cv, _ in caps]
+        nr = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) if normals else None
+              for cv, _ in caps]
+        col = [torch.zeros(max(cv, 1), dtype=torch.int32, device=dev) for cv, _ in caps]
+        f = [torch.zeros((max(cf, 1), 3), dtype=torch.int32, device=dev) for _, cf in caps]
+        ptrs = lambda xs: (C.c_void_p * m)(*[None if x is None else x.data_ptr() for x in xs])
+        _fills_done()
+        try:
+            self._check(fn(self.h, n, arr, tarr, carr, ptrs(v), ptrs(nr) if normals else None,
+                           ptrs(col), ptrs(f), (C.c_size_t * m)(*[c[0] for c in caps]),
+                           (C.c_size_t * m)(*[c[1] for c in caps]), nv, nf), "stream_tubes")
+        except SprayRtError as e:
+            e.counts = [(nv[i], nf[i]) for i in range(n)]
+            e.buffers = tuple(b for b in (v, nr, col, f) if n and b[0] is not None)
+            raise
+        return [(v[i][:nv[i]], nr[i][:nv[i]] if normals else None, col[i][:nv[i]], f[i][:nf[i]])
+                for i in range(n)]
+
+    def stream_tubes_domains(self, slots, fields, tubes, normals=True, bounds=None):
+        """spray_rt_domains_stream_tubes: the tubes of stream_tubes() into slots
+        (empty or loaded), traced, expanded and built on the device; a slot
+        carries colours when its field has a cfield or its tube a color.
+        bounds as in refit_domains -> (bounds result, triangle counts)."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(fields) != n:
+            e = SprayRtError("stream_tubes_domains: %d slots, %d fields" % (n, len(fields)))
+            e.code = -1
+            raise e
+        arr, tarr, carr, keep = _stream_tables(fields, tubes)
+        m = max(n, 1)
+        sl = (C.c_int * m)(*slots)
+        out = self._bounds_out(bounds, n)
+        b, k = _addr(out)
+        nf = (C.c_size_t * m)()
+        self._check(lib().spray_rt_domains_stream_tubes(
+            self.h, n, sl, arr, tarr, carr, 1 if normals else 0, b, nf), "domains_stream_tubes")
+        for s in slots:
+            self._nverts.pop(s, None)  # the vertex count is the expansion's
+        if bounds is True:
+            self.sync()
+            out = out[:n].cpu().numpy()
+        return out, [nf[i] for i in range(n)]
+
+    def stream_phase_times(self):
+        """spray_rt_stream_phase_times of the last streamline call -> [ms to the
+        end of the host read, ms of the second integration and the expansion,
+        ms of the device build]."""
+        out = (C.c_double * 3)()
+        self._check(lib().spray_rt_stream_phase_times(self.h, out), "stream_phase_times")
+        return list(out)
 
     def slot_export(self, slot, what):
         """One array of a resident slot as numpy: SLOT_NODES / SLOT_QNODES4 as
