@@ -1,5 +1,7 @@
 """A numpy restatement of the streamline rule and the fields and seeds shared
-by the streamline tests (test_streamlines_host.py, test_gpu_streamlines.py).
+by the streamline tests (test_streamlines_host.py, test_gpu_streamlines.py,
+test_stream_cases.py, test_gpu_stream_cases.py; the hard classes are in
+stream_cases.py).
 
 Written from the rule in include/spray_rt.h, step by step, not from the C
 code: sample, step, lines, tangent and frame, tube.  Every operation is one
@@ -109,15 +111,19 @@ class Rule:
         hh, h6 = F(0.5) * h, h / F(6.0)
         k2 = self.v_at(p + hh * k1)
         if k2 is None:
+            self.stats["grid_q2"] += 1
             return None, GRID
         k3 = self.v_at(p + hh * k2)
         if k3 is None:
+            self.stats["grid_q3"] += 1
             return None, GRID
         k4 = self.v_at(p + h * k3)
         if k4 is None:
+            self.stats["grid_q4"] += 1
             return None, GRID
         pn = p + h6 * (((k1 + F(2) * k2) + F(2) * k3) + k4)
         if not self.locate(pn)[0]:
+            self.stats["grid_pn"] += 1
             return None, GRID
         if pn.tobytes() == p.tobytes():
             self.stats["no_motion"] += 1
@@ -132,6 +138,9 @@ class Rule:
         for b in (1, 2):
             if abs(T[b]) < abs(T[a]):
                 a = b
+        if sum(abs(T[b]) == abs(T[a]) for b in range(3)) > 1:
+            self.stats["axis_tie"] += 1   # the smallest |T_a| on two or three axes
+        self.stats["axis_%d" % a] += 1
         e = np.zeros(3, F)
         e[a] = 1
         w = e - T[a] * T
@@ -156,6 +165,7 @@ class Rule:
             else:
                 w = N - dot(N, T) * T
                 if dot(w, w) >= F(0.25):
+                    self.stats["carried"] += 1
                     N = w / np.sqrt(dot(w, w))
                 else:
                     self.stats["repick"] += 1
