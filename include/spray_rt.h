@@ -959,6 +959,155 @@ int spray_rt_tube_ring_host(int32_t nsides, float out[][2]);
  * (their enqueue; completed where an array was staged from the host), [2] the
  * device build of the domains form (its two host reads wait for [1]'s work). */
 int spray_rt_stream_phase_times(spray_rt_ctx_t ctx, double out_ms[3]);
+/* ---- glyphs of point sets: spheres and arrows ---- */
+#define SPRAY_RT_GLYPH_SPHERE 0
+#define SPRAY_RT_GLYPH_ARROW  1
+/* One set of points, what a particle code leaves in HBM, and which of them to
+ * draw. */
+typedef struct spray_rt_pointset {
+  const float* points;   /* [npoints][3]; device or host memory */
+  size_t npoints;
+  const float* vectors;  /* [npoints][3] or NULL; required for ARROW */
+  const float* scales;   /* [npoints] or NULL: per-point factor, finite, >= 0 */
+  const float* select;   /* [npoints] or NULL: kept when select_lo <= v <= select_hi */
+  float select_lo, select_hi; /* read with select only */
+  uint32_t stride;       /* >= 1: only points with i % stride == 0 are candidates */
+} spray_rt_pointset;
+/* The glyph drawn at every kept point of a set. */
+typedef struct spray_rt_glyph {
+  int32_t shape;            /* SPRAY_RT_GLYPH_* */
+  float size;               /* > 0, finite: sphere radius / arrow length unit */
+  int32_t level;            /* SPHERE: icosphere level 0..3 (20, 80, 320, 1280 faces) */
+  int32_t nsides;           /* ARROW: 3..16 */
+  int32_t scale_by_vector;  /* ARROW: length = size * |v| instead of size */
+  float min_speed;          /* ARROW: > 0, its square a normal float (as spray_rt_vecfield) */
+  uint32_t color_rgb;       /* one colour for every vertex ... */
+  int32_t has_color;        /* ... or none (spray_rt_domains_glyphs only) */
+} spray_rt_glyph;
+/* The rule is fixed, so that the kernels and the host restatement agree byte
+ * for byte: float, no contraction, division and square
+ * root correctly rounded.  dot, normalised, the cross product and the axis
+ * rule are the streamlines' above.
+ *
+ * Keep.  Point i is a candidate when i % stride == 0 and, with select, when
+ * select_lo <= select[i] && select[i] <= select_hi.  Its factor is s = size *
+ * scales[i] (size without scales); for an arrow d = (vx * vx + vy * vy) + vz *
+ * vz, and with scale_by_vector s = (size * scales[i]) * sqrtf(d).  A candidate
+ * is kept when 0 < s && s < inf, and for an arrow when also msq <= d && d <
+ * inf, msq = min_speed * min_speed.  A subnormal s is kept; an s that
+ * overflows, or is zero, drops the point without an error.
+ *
+ * Order.  Glyph g is the g-th kept point in point order; point_ids[g] is that
+ * point.  Every glyph of a set has V vertices and F faces; its vertex k is
+ * vertex g * V + k of the set, its face r face g * F + r = its table row +
+ * g * V.  Ng = (v0 - v1) x (v2 - v0) points away from the glyph.  The colour
+ * of all V vertices is map(field[i]) (spray_rt_grid_color, field one float per
+ * point), else color_rgb.
+ *
+ * Sphere.  V = 10 * 4^level + 2, F = 20 * 4^level, (u_k, faces) =
+ * spray_rt_glyph_sphere_host(level).  Vertex k is at p + s * u_k per
+ * component, its normal u_k.
+ *
+ * Arrow.  T = v / sqrtf(d) per component, N = the axis rule's normal of T, B =
+ * T x N, L = s.  rs = 0.03f * L, rh = 0.1f * L, hl = 0.35f * L, ls = L - hl;
+ * (c_k, s_k) = spray_rt_tube_ring_host(nsides), off_k = c_k * N + s_k * B per
+ * component; cone_k = cn * off_k + ct * T with cn = (float)(0.35 / hypot(0.35,
+ * 0.1)), ct = (float)(0.1 / hypot(0.35, 0.1)), both evaluated in double on the
+ * host.  V = 4 * nsides + 1; vertex j * nsides + k is
+ *   j = 0   p + rs * off_k                normal off_k
+ *   j = 1   (p + ls * T) + rs * off_k     normal off_k
+ *   j = 2   (p + ls * T) + rh * off_k     normal cone_k
+ *   j = 3   p + L * T (for every k)       normal cone_k
+ * and vertex 4 * nsides is the tail centre p with normal -T.  F = 6 * nsides:
+ * with (j, k) = vertex j * nsides + k and k' = k + 1 mod nsides, for k = 0 ..
+ * nsides - 1 the shaft's ((0, k), (1, k), (0, k')) and ((0, k'), (1, k), (1,
+ * k')); then the annulus' ((1, k), (2, k), (1, k')) and ((1, k'), (2, k), (2,
+ * k')); then the cone's ((2, k), (3, k), (2, k')); then the tail fan's
+ * (centre, (0, k), (0, k')).  The nsides tip vertices share one position and
+ * differ in their normals.
+ *
+ * No atomic decides an index, two runs give the same bytes.
+ *
+ * spray_rt_glyphs expands n sets in one batched call on the context's stream
+ * into the caller's device buffers, with the conventions of
+ * spray_rt_stream_tubes: verts / vnormals / colors / faces / point_ids, or
+ * single entries, may be NULL independently, all NULL only counts; point_ids[i]
+ * is uint32 [cap_verts[i] / V] and counts as a per-vertex array for the
+ * capacity.  gcolors (optional) is an array of colour maps, field one float per
+ * point; a set without one takes color_rgb.  nverts_out / nfaces_out (host,
+ * optional) are written on return: the call's one host read.  A capacity that
+ * is too small gives SPRAY_RT_ERR_LIMIT with the counts reported and nothing
+ * written.
+ *
+ * Errors, before anything is written, naming the set: SPRAY_RT_ERR_ARG for a
+ * NULL pointer with a nonzero count, stride == 0, a bad size, shape, level,
+ * nsides or min_speed, with select a range that is not lo <= hi, both finite,
+ * ARROW without vectors, the colour map errors of spray_rt_isosurface_mapped;
+ * and, found by a check pass and reported at the host read, a non-finite
+ * point, vector, scale, select value or colour sample or a negative scale,
+ * anywhere in an array the call uses (a sphere set may carry vectors: they are
+ * not read).  SPRAY_RT_ERR_LIMIT for 2^31 or more points, 2^32 or more
+ * vertices, 2^29 or more faces; a sphere set without select and scales keeps
+ * every candidate, so its totals are checked from the counts before an array
+ * is read. */
+int spray_rt_glyphs(spray_rt_ctx_t ctx, int n, const spray_rt_pointset* sets,
+                    const spray_rt_glyph* glyphs, const spray_rt_grid_color* gcolors,
+                    float* const* verts, float* const* vnormals, uint32_t* const* colors,
+                    uint32_t* const* faces, uint32_t* const* point_ids, const size_t* cap_verts,
+                    const size_t* cap_faces, size_t* nverts_out, size_t* nfaces_out);
+/* Point sets in, resident slots out: afterwards slots[i] is a slot of
+ * spray_rt_domains_build of the glyph mesh of sets[i] (with its normals if
+ * with_normals, its colours if it has a colour field or has_color), byte for
+ * byte.  d_bounds and nfaces_out as in spray_rt_domains_isosurface.  At most
+ * three host reads (the counts, and the build's two).  A failed call leaves
+ * every slot as it was; the errors above, a bad slot or a slot listed twice
+ * (SPRAY_RT_ERR_ARG), and the build's.  spray_rt_last_error names the set and
+ * the slot.  A set that keeps no point gives the empty slot an empty upload
+ * gives.  Not for use while lanes run.
+ *
+ * Moving particles: when the kept set is unchanged from one timestep to the
+ * next, the cheap path is spray_rt_glyphs with verts (and vnormals) alone on
+ * the new positions, then spray_rt_domains_refit with those device pointers: a
+ * refit instead of a build.  That relies on the keep decisions (stride, select,
+ * scales, speeds) being the ones the slot was built from; the nverts check
+ * catches most mismatches, not all.  Recolouring by another field is the same
+ * pattern: spray_rt_glyphs with colors alone, then spray_rt_domains_recolor. */
+int spray_rt_domains_glyphs(spray_rt_ctx_t ctx, int n, const int* slots,
+                            const spray_rt_pointset* sets, const spray_rt_glyph* glyphs,
+                            const spray_rt_grid_color* gcolors, int with_normals, float* d_bounds,
+                            size_t* nfaces_out);
+/* Host-only restatement (no GPU; the arrays are host memory): the arrays the
+ * kernels write, byte for byte.  The sizes are always reported; any output may
+ * be NULL (verts_out / vnormals_out float[*nverts][3], colors_out
+ * uint32[*nverts], faces_out uint32[*nfaces][3], point_ids_out uint32[*nverts /
+ * V]).  gcolor may be NULL. */
+int spray_rt_glyphs_host(const spray_rt_pointset* set, const spray_rt_glyph* glyph,
+                         const spray_rt_grid_color* gcolor, size_t* nverts, size_t* nfaces,
+                         float* verts_out, float* vnormals_out, uint32_t* colors_out,
+                         uint32_t* faces_out, uint32_t* point_ids_out);
+/* The unit icosphere table the spheres use, level 0 .. 3: exposed so that a
+ * restatement need not reproduce it.  Built in double.  Level 0 is the
+ * icosahedron on (0, +-1, +-t), (+-1, +-t, 0), (+-t, 0, +-1), t = (1 + sqrt(5)) /
+ * 2, in the order (-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t),
+ * (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t,
+ * 0, 1), each divided by its length, with the faces (0 5 11) (0 1 5) (0 7 1)
+ * (0 10 7) (0 11 10) (1 9 5) (5 4 11) (11 2 10) (10 6 7) (7 8 1) (3 4 9)
+ * (3 2 4) (3 6 2) (3 8 6) (3 9 8) (4 5 9) (2 11 4) (6 10 2) (8 7 6) (9 1 8).
+ * A subdivision keeps the vertices and walks the faces in order: face (a, b,
+ * c) asks for the midpoints ab, bc, ca in that order, a new midpoint takes the
+ * next vertex number and is 0.5 * (v_lo + v_hi) of the edge's lower- and
+ * higher-numbered end divided by its length, and the face becomes (a, ab, ca),
+ * (b, bc, ab), (c, ca, bc), (ab, bc, ca).  Every coordinate is cast to float
+ * at the end.  *nverts = 10 * 4^level + 2, *nfaces = 20 * 4^level; either
+ * output may be NULL.  SPRAY_RT_ERR_ARG for another level. */
+int spray_rt_glyph_sphere_host(int32_t level, size_t* nverts, size_t* nfaces, float* verts_out,
+                               uint32_t* faces_out);
+/* Wall-clock milliseconds of the last glyph call of the context: out_ms[0] to
+ * the end of the host read (staging, the check, count and scan passes), [1]
+ * the place pass and the expansion (their enqueue; completed where an array
+ * was staged from the host), [2] the device build of the domains form (its two
+ * host reads wait for [1]'s work). */
+int spray_rt_glyph_phase_times(spray_rt_ctx_t ctx, double out_ms[3]);
 /* Read back one array of a resident slot (tests, debugging): *nbytes = its
  * size; with out, copied there (cap_bytes >= the size) after the queued work
  * on the context's stream.  Slots without the quantized copy report 0 bytes

@@ -105,6 +105,23 @@ class Tube(C.Structure):
 
 assert C.sizeof(VecField) == 80 and C.sizeof(Tube) == 16
 
+
+class PointSet(C.Structure):
+    """spray_rt_pointset."""
+    _fields_ = [("points", C.c_void_p), ("npoints", C.c_size_t), ("vectors", C.c_void_p),
+                ("scales", C.c_void_p), ("select", C.c_void_p), ("select_lo", C.c_float),
+                ("select_hi", C.c_float), ("stride", C.c_uint32)]
+
+
+class Glyph(C.Structure):
+    """spray_rt_glyph."""
+    _fields_ = [("shape", C.c_int32), ("size", C.c_float), ("level", C.c_int32),
+                ("nsides", C.c_int32), ("scale_by_vector", C.c_int32), ("min_speed", C.c_float),
+                ("color_rgb", C.c_uint32), ("has_color", C.c_int32)]
+
+
+assert C.sizeof(PointSet) == 56 and C.sizeof(Glyph) == 32
+
 # every symbol the public headers declare: (restype, argtypes)
 P = C.c_void_p
 SZ = C.c_size_t
@@ -164,6 +181,11 @@ SIGNATURES = {
     "spray_rt_stream_tubes_host": (I, [P, P, P, P, P, P, P, P, P]),
     "spray_rt_tube_ring_host": (I, [C.c_int32, P]),
     "spray_rt_stream_phase_times": (I, [P, P]),
+    "spray_rt_glyphs": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_glyphs": (I, [P, I, P, P, P, P, I, P, P]),
+    "spray_rt_glyphs_host": (I, [P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_glyph_sphere_host": (I, [C.c_int32, P, P, P, P]),
+    "spray_rt_glyph_phase_times": (I, [P, P]),
     "spray_rt_slot_export": (I, [P, I, I, P, SZ, P]),
     "spray_rt_slot_sah": (I, [P, I, P]),
     "spray_rt_intersect1M": (I, [P, I, P, SZ, SZ]),

@@ -21,7 +21,8 @@ __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_r
            "cell_isosurface_host", "cell_split_host", "cell_surface_host", "cell_clip_host",
            "plane_values_host", "streamlines_host", "stream_tubes_host", "tube_ring",
            "STREAM_FORWARD", "STREAM_BACKWARD", "STREAM_BOTH", "LINE_END_GRID", "LINE_END_STEPS",
-           "LINE_END_SPEED", "LINE_END_SEED", "SLOT_COLORS",
+           "LINE_END_SPEED", "LINE_END_SEED", "glyphs_host", "glyph_sphere", "GLYPH_SPHERE",
+           "GLYPH_ARROW", "SLOT_COLORS",
            "SLOT_FACES",
            "host_parse_scene", "host_scene_bsdfs",
            "host_domain_mesh", "RAY_DTYPE",
@@ -791,6 +792,131 @@ def tube_ring(nsides):
         e.code = rc
         raise e
     return out
+
+
+GLYPH_SPHERE, GLYPH_ARROW = 0, 1
+
+
+def _glyph_array(x, what, tail, n=None):
+    """A float32 numpy array or GPU tensor of shape [n, *tail]."""
+    if hasattr(x, "data_ptr"):
+        if x.element_size() != 4 or not x.is_floating_point():
+            raise TypeError("glyphs: %s are float32" % what)
+    else:
+        x = np.ascontiguousarray(x, np.float32)
+    shape = tuple(int(d) for d in x.shape)
+    if len(shape) != 1 + len(tail) or shape[1:] != tuple(tail) or (n is not None and shape[0] != n):
+        raise ValueError("glyphs: %s are a [npoints%s] array"
+                         % (what, "".join(", %d" % t for t in tail)))
+    return x
+
+
+def _glyph_tables(sets, glyphs):
+    """sets: dicts with the key points (float32 [npoints, 3]) and optionally
+    vectors (float32 [npoints, 3]), scales, select (float32 [npoints]),
+    select_range = (lo, hi), stride (1), cfield (float32 [npoints]) and cmap =
+    (table uint32[n], lo, hi); arrays are numpy arrays or torch tensors on the
+    GPU.  glyphs: dicts with shape (GLYPH_SPHERE / GLYPH_ARROW), size and
+    optionally level (1), nsides (8), scale_by_vector (False), min_speed (1e-6),
+    color, one per set or one for all -> (spray_rt_pointset array,
+    spray_rt_glyph array, spray_rt_grid_color array, keepalive)."""
+    from ._native import Glyph, PointSet
+    if isinstance(glyphs, dict):
+        glyphs = [glyphs] * len(sets)
+    if len(glyphs) != len(sets):
+        raise ValueError("glyphs: one glyph per set")
+    m = max(len(sets), 1)
+    arr, garr, carr = (PointSet * m)(), (Glyph * m)(), (_GridColor * m)()
+    keep = []
+    for S, rec, crec in zip(sets, arr, carr):
+        pts = _glyph_array(S["points"], "points", (3,))
+        n = int(pts.shape[0])
+        keep.append(pts)
+        rec.points = _addr(pts)[0] if n else None
+        rec.npoints = n
+        for key, tail in (("vectors", (3,)), ("scales", ()), ("select", ())):
+            x = S.get(key)
+            if x is not None:
+                x = _glyph_array(x, key, tail, n)
+                keep.append(x)
+                setattr(rec, key, _addr(x)[0] if n else None)
+        lo, hi = S.get("select_range", (0.0, 0.0))
+        rec.select_lo, rec.select_hi = float(lo), float(hi)
+        rec.stride = int(S.get("stride", 1))
+        cf = S.get("cfield")
+        if cf is not None:
+            cf = _glyph_array(cf, "colour fields", (), n)
+            keep.append(cf)
+            crec.field = _addr(cf)[0] if n else None
+            if n and S.get("cmap") is not None:
+                t, crec.table_rgb, crec.ntable, crec.lo, crec.hi = _cmap_args(S["cmap"])
+                keep.append(t)
+    for G, rec in zip(glyphs, garr):
+        rec.shape = int(G["shape"])
+        rec.size = float(G["size"])
+        rec.level = int(G.get("level", 1))
+        rec.nsides = int(G.get("nsides", 8))
+        rec.scale_by_vector = 1 if G.get("scale_by_vector") else 0
+        rec.min_speed = float(G.get("min_speed", 1e-6))
+        color = G.get("color")
+        rec.has_color = 0 if color is None else 1
+        rec.color_rgb = 0 if color is None else int(color)
+    return arr, garr, carr, keep
+
+
+def _glyph_counts(arr, garr, i, nv):
+    """Glyphs of set i from its vertex count."""
+    g = garr[i]
+    V = 10 * 4 ** g.level + 2 if g.shape == GLYPH_SPHERE else 4 * g.nsides + 1
+    return nv // V
+
+
+def glyphs_host(pointset, glyph, normals=True, count_only=False, point_ids=True):
+    """spray_rt_glyphs_host (no GPU): the glyph mesh RtContext.glyphs builds of
+    one set (see _glyph_tables) -> (verts float32 [nv, 3], normals float32
+    [nv, 3] or None, colors uint32 [nv], faces uint32 [nf, 3], point_ids uint32
+    [nglyphs] or None); count_only: (nv, nf)."""
+    arr, garr, carr, keep = _glyph_tables([pointset], [glyph])
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_glyphs_host(C.addressof(arr), C.addressof(garr), C.addressof(carr),
+                                    C.byref(nv), C.byref(nf), *outs)
+        if rc != 0:
+            e = SprayRtError("glyphs_host failed (%d)" % rc)
+            e.code = rc
+            e.counts = (nv.value, nf.value)
+            raise e
+
+    call(None, None, None, None, None)
+    if count_only:
+        return nv.value, nf.value
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals else None
+    c = np.zeros(nv.value, np.uint32)
+    fc = np.zeros((nf.value, 3), np.uint32)
+    ids = np.zeros(_glyph_counts(arr, garr, 0, nv.value), np.uint32) if point_ids else None
+    call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, fc.ctypes.data,
+         None if ids is None else ids.ctypes.data)
+    return v, n, c, fc, ids
+
+
+def glyph_sphere(level):
+    """spray_rt_glyph_sphere_host: the unit icosphere table of the sphere
+    glyphs -> (verts float32 [V, 3], faces uint32 [F, 3])."""
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+    rc = L.spray_rt_glyph_sphere_host(int(level), C.byref(nv), C.byref(nf), None, None)
+    if rc == 0:
+        v = np.zeros((nv.value, 3), np.float32)
+        f = np.zeros((nf.value, 3), np.uint32)
+        rc = L.spray_rt_glyph_sphere_host(int(level), None, None, v.ctypes.data, f.ctypes.data)
+    if rc != 0:
+        e = SprayRtError("glyph_sphere failed (%d)" % rc)
+        e.code = rc
+        raise e
+    return v, f
 
 
 def host_parse_scene(desc, ply_path=""):
@@ -1689,6 +1815,94 @@ class RtContext:
         ms of the device build]."""
         out = (C.c_double * 3)()
         self._check(lib().spray_rt_stream_phase_times(self.h, out), "stream_phase_times")
+        return list(out)
+
+    # ---- glyphs ----
+    def glyphs(self, sets, glyphs, normals=True, capacity=None, count_only=False, arrays=None):
+        """spray_rt_glyphs: the kept points of sets as spheres or arrows (see
+        _glyph_tables) in one batched call -> [(verts float32 [nv, 3], normals
+        float32 [nv, 3] or None, colors int32 [nv] holding the 0x00RRGGBB bits,
+        faces int32 [nf, 3] and point_ids int32 [nglyphs] holding the uint32
+        bits)] as GPU tensors.  capacity=(nverts, nfaces) and count_only as in
+        stream_tubes (count_only: [(nv, nf)]).  arrays: the subset of ("verts",
+        "normals", "colors", "faces", "point_ids") to extract, the others None
+        (verts and normals alone feed refit_domains, colors alone
+        recolor_domains)."""
+        import torch
+        n = len(sets)
+        arr, garr, carr, keep = _glyph_tables(sets, glyphs)
+        m = max(n, 1)
+        nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        fn = lib().spray_rt_glyphs
+        if capacity is None or count_only:
+            self._check(fn(self.h, n, arr, garr, carr, None, None, None, None, None, None, None,
+                           nv, nf), "glyphs")
+            if count_only:
+                return [(nv[i], nf[i]) for i in range(n)]
+            caps = [(nv[i], nf[i]) for i in range(n)]
+        else:
+            caps = [(int(capacity[0]), int(capacity[1]))] * n
+        dev = "cuda:%d" % self._device
+        want = set(("verts", "normals", "colors", "faces", "point_ids") if arrays is None else arrays)
+        if not normals:
+            want.discard("normals")
+        # zeroed, one element at least: a buffer a failed call must not touch
+        zeros = lambda name, shape, dt: (torch.zeros(shape, dtype=dt, device=dev)
+                                         if name in want else None)
+        v = [zeros("verts", (max(cv, 1), 3), torch.float32) for cv, _ in caps]
+        nr = [zeros("normals", (max(cv, 1), 3), torch.float32) for cv, _ in caps]
+        col = [zeros("colors", max(cv, 1), torch.int32) for cv, _ in caps]
+        f = [zeros("faces", (max(cf, 1), 3), torch.int32) for _, cf in caps]
+        ids = [zeros("point_ids", max(_glyph_counts(arr, garr, i, caps[i][0]), 1), torch.int32)
+               for i in range(n)]
+        ptrs = lambda name, xs: ((C.c_void_p * m)(*[x.data_ptr() for x in xs])
+                                 if n and name in want else None)
+        _fills_done()
+        try:
+            self._check(fn(self.h, n, arr, garr, carr, ptrs("verts", v), ptrs("normals", nr),
+                           ptrs("colors", col), ptrs("faces", f), ptrs("point_ids", ids),
+                           (C.c_size_t * m)(*[c[0] for c in caps]),
+                           (C.c_size_t * m)(*[c[1] for c in caps]), nv, nf), "glyphs")
+        except SprayRtError as e:
+            e.counts = [(nv[i], nf[i]) for i in range(n)]
+            e.buffers = tuple(b for b in (v, nr, col, f, ids) if n and b[0] is not None)
+            raise
+        cut = lambda x, k: None if x is None else x[:k]
+        return [(cut(v[i], nv[i]), cut(nr[i], nv[i]), cut(col[i], nv[i]), cut(f[i], nf[i]),
+                 cut(ids[i], _glyph_counts(arr, garr, i, nv[i]))) for i in range(n)]
+
+    def glyphs_domains(self, slots, sets, glyphs, normals=True, bounds=None):
+        """spray_rt_domains_glyphs: the glyph meshes of glyphs() into slots
+        (empty or loaded), expanded and built on the device; a slot carries
+        colours when its set has a cfield or its glyph a color.  bounds as in
+        refit_domains -> (bounds result, triangle counts)."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(sets) != n:
+            e = SprayRtError("glyphs_domains: %d slots, %d sets" % (n, len(sets)))
+            e.code = -1
+            raise e
+        arr, garr, carr, keep = _glyph_tables(sets, glyphs)
+        m = max(n, 1)
+        sl = (C.c_int * m)(*slots)
+        out = self._bounds_out(bounds, n)
+        b, k = _addr(out)
+        nf = (C.c_size_t * m)()
+        self._check(lib().spray_rt_domains_glyphs(
+            self.h, n, sl, arr, garr, carr, 1 if normals else 0, b, nf), "domains_glyphs")
+        for s in slots:
+            self._nverts.pop(s, None)  # the vertex count is the expansion's
+        if bounds is True:
+            self.sync()
+            out = out[:n].cpu().numpy()
+        return out, [nf[i] for i in range(n)]
+
+    def glyph_phase_times(self):
+        """spray_rt_glyph_phase_times of the last glyph call -> [ms to the end
+        of the host read, ms of the place pass and the expansion, ms of the
+        device build]."""
+        out = (C.c_double * 3)()
+        self._check(lib().spray_rt_glyph_phase_times(self.h, out), "glyph_phase_times")
         return list(out)
 
     def slot_export(self, slot, what):
