@@ -959,6 +959,98 @@ int spray_rt_tube_ring_host(int32_t nsides, float out[][2]);
  * (their enqueue; completed where an array was staged from the host), [2] the
  * device build of the domains form (its two host reads wait for [1]'s work). */
 int spray_rt_stream_phase_times(spray_rt_ctx_t ctx, double out_ms[3]);
+/* ---- streamlines across the blocks of a multi-block vector field ---- */
+/* One block of a set: a structured grid of vectors as in spray_rt_vecfield. */
+typedef struct spray_rt_vecblock {
+  const float* vectors;     /* [nz][ny][nx][3], x fastest; device or host memory */
+  const float* color_field; /* optional [nz][ny][nx]; all blocks of a set have one, or none */
+  int32_t dims[3];          /* each >= 2 */
+  float origin[3];
+  float spacing[3];
+} spray_rt_vecblock;
+/* A set of blocks, the seeds to trace from and how.  Blocks may differ in dims
+ * and spacing, share a face plane, overlap or leave gaps. */
+typedef struct spray_rt_blockfield {
+  const spray_rt_vecblock* blocks; /* host array */
+  int32_t nblocks;                 /* 1 .. 65535 */
+  const float* seeds;              /* [nseeds][3] world positions; device or host memory */
+  size_t nseeds;
+  float step;                      /* the four as in spray_rt_vecfield */
+  int32_t max_steps;
+  int32_t direction;
+  float min_speed;
+} spray_rt_blockfield;
+/* The colour map of a set whose blocks have colour fields: the table of
+ * spray_rt_grid_color. */
+typedef struct spray_rt_block_color {
+  const uint32_t* table_rgb; /* NULL: the set has no map */
+  int32_t ntable;
+  float lo, hi;
+} spray_rt_block_color;
+/* The rule is the streamlines' above, unchanged: sample, step, end reasons and
+ * their order, lines, tangent and frame, tube, ring table.  Only "which grid"
+ * changes.  A half-line carries a current block b.  A
+ * sample at q is taken in b if q is inside b by the test above (0 <= g <=
+ * float(n - 1) on all axes with b's origin, spacing and dims; a NaN fails);
+ * otherwise in the lowest-indexed block of the set that q is inside, and that
+ * block becomes the current one; if q is inside no block the sample fails as a
+ * sample outside the grid does above: a seed inside no block gives SEED, a
+ * stage point or p' inside no block gives GRID.  The current block is updated
+ * at every successful locate in program order q2, q3, q4, p', so the block
+ * that p's frame, colour and next k1 are sampled in is the one p was located
+ * in as p'.  Both halves of a line start from the lowest-indexed block that
+ * contains the seed.  The colour of a point is map(g(p)), g the trilinear
+ * sample of its block's color_field, else color_rgb.
+ *
+ * A set of one block gives the bytes of spray_rt_streamlines and
+ * spray_rt_stream_tubes on that grid.  Index sub-boxes of a grid with origin 0
+ * and power-of-two spacings, sharing planes, give the unsplit grid's bytes as
+ * long as no located point lies exactly on a shared plane: p - origin is then
+ * exact, so g, the cell and f are the same real numbers in either.
+ *
+ * spray_rt_block_streamlines, spray_rt_block_stream_tubes and
+ * spray_rt_domains_block_stream_tubes are spray_rt_streamlines,
+ * spray_rt_stream_tubes and spray_rt_domains_stream_tubes over n sets, with
+ * their conventions: NULL arrays or entries, counting only, one host read (at
+ * most three for the domains form), SPRAY_RT_ERR_LIMIT with the counts reported
+ * and nothing written, failed calls leaving buffers and slots as they were.
+ * point_blocks[i] (optional) is uint32 [cap_points[i]]: the block each point
+ * was sampled in.  bcolors (optional) is one spray_rt_block_color per set.  A
+ * whole set's tubes go into one slot.
+ *
+ * Errors are the streamlines', spray_rt_last_error naming the set and, where
+ * one is at fault, the block; also SPRAY_RT_ERR_ARG for nblocks outside 1 ..
+ * 65535, NULL blocks or block vectors, colour fields on some blocks of a set
+ * but not on all, a bcolors entry with a table for a set whose blocks have no
+ * colour field; SPRAY_RT_ERR_LIMIT for 2^31 or more points in one block. */
+int spray_rt_block_streamlines(spray_rt_ctx_t ctx, int n, const spray_rt_blockfield* sets,
+                               float* const* points, uint32_t* const* line_offsets,
+                               uint32_t* const* line_info, uint32_t* const* point_blocks,
+                               const size_t* cap_points, size_t* npoints_out);
+int spray_rt_block_stream_tubes(spray_rt_ctx_t ctx, int n, const spray_rt_blockfield* sets,
+                                const spray_rt_tube* tubes, const spray_rt_block_color* bcolors,
+                                float* const* verts, float* const* vnormals,
+                                uint32_t* const* colors, uint32_t* const* faces,
+                                const size_t* cap_verts, const size_t* cap_faces,
+                                size_t* nverts_out, size_t* nfaces_out);
+int spray_rt_domains_block_stream_tubes(spray_rt_ctx_t ctx, int n, const int* slots,
+                                        const spray_rt_blockfield* sets,
+                                        const spray_rt_tube* tubes,
+                                        const spray_rt_block_color* bcolors, int with_normals,
+                                        float* d_bounds, size_t* nfaces_out);
+/* Host-only restatements of one set (no GPU; every array is host memory): the
+ * arrays the kernels write, byte for byte, as spray_rt_streamlines_host and
+ * spray_rt_stream_tubes_host; point_blocks_out uint32[*npoints].  bcolor may be
+ * NULL. */
+int spray_rt_block_streamlines_host(const spray_rt_blockfield* set, size_t* npoints,
+                                    float* points_out, uint32_t* line_offsets_out,
+                                    uint32_t* line_info_out, uint32_t* point_blocks_out);
+int spray_rt_block_stream_tubes_host(const spray_rt_blockfield* set, const spray_rt_tube* tube,
+                                     const spray_rt_block_color* bcolor, size_t* nverts,
+                                     size_t* nfaces, float* verts_out, float* vnormals_out,
+                                     uint32_t* colors_out, uint32_t* faces_out);
+/* spray_rt_stream_phase_times of the last block streamline call. */
+int spray_rt_block_stream_phase_times(spray_rt_ctx_t ctx, double out_ms[3]);
 /* ---- glyphs of point sets: spheres and arrows ---- */
 #define SPRAY_RT_GLYPH_SPHERE 0
 #define SPRAY_RT_GLYPH_ARROW  1

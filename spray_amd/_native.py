@@ -106,6 +106,28 @@ class Tube(C.Structure):
 assert C.sizeof(VecField) == 80 and C.sizeof(Tube) == 16
 
 
+class VecBlock(C.Structure):
+    """spray_rt_vecblock."""
+    _fields_ = [("vectors", C.c_void_p), ("color_field", C.c_void_p), ("dims", C.c_int32 * 3),
+                ("origin", C.c_float * 3), ("spacing", C.c_float * 3)]
+
+
+class BlockField(C.Structure):
+    """spray_rt_blockfield."""
+    _fields_ = [("blocks", C.c_void_p), ("nblocks", C.c_int32), ("seeds", C.c_void_p),
+                ("nseeds", C.c_size_t), ("step", C.c_float), ("max_steps", C.c_int32),
+                ("direction", C.c_int32), ("min_speed", C.c_float)]
+
+
+class BlockColor(C.Structure):
+    """spray_rt_block_color."""
+    _fields_ = [("table_rgb", C.c_void_p), ("ntable", C.c_int32), ("lo", C.c_float),
+                ("hi", C.c_float)]
+
+
+assert C.sizeof(VecBlock) == 56 and C.sizeof(BlockField) == 48 and C.sizeof(BlockColor) == 24
+
+
 class PointSet(C.Structure):
     """spray_rt_pointset."""
     _fields_ = [("points", C.c_void_p), ("npoints", C.c_size_t), ("vectors", C.c_void_p),
@@ -181,6 +203,12 @@ SIGNATURES = {
     "spray_rt_stream_tubes_host": (I, [P, P, P, P, P, P, P, P, P]),
     "spray_rt_tube_ring_host": (I, [C.c_int32, P]),
     "spray_rt_stream_phase_times": (I, [P, P]),
+    "spray_rt_block_streamlines": (I, [P, I, P, P, P, P, P, P, P]),
+    "spray_rt_block_stream_tubes": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P]),
+    "spray_rt_domains_block_stream_tubes": (I, [P, I, P, P, P, P, I, P, P]),
+    "spray_rt_block_streamlines_host": (I, [P, P, P, P, P, P]),
+    "spray_rt_block_stream_tubes_host": (I, [P, P, P, P, P, P, P, P, P]),
+    "spray_rt_block_stream_phase_times": (I, [P, P]),
     "spray_rt_glyphs": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "spray_rt_domains_glyphs": (I, [P, I, P, P, P, P, I, P, P]),
     "spray_rt_glyphs_host": (I, [P, P, P, P, P, P, P, P, P, P]),

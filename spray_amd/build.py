@@ -30,14 +30,16 @@ SOURCES = ["rt_kernels.hip", "ooc_kernels.hip", "frame_kernels.hip", "insitu_ker
            "build_device.cpp", "iso_kernels.hip", "isosurface.cpp", "tet_kernels.hip",
            "tet_isosurface.cpp", "cell_kernels.hip", "cell_isosurface.cpp", "surf_kernels.hip",
            "cell_surface.cpp", "clip_kernels.hip", "cell_clip.cpp", "stream_kernels.hip",
-           "streamlines.cpp", "glyph_kernels.hip", "glyphs.cpp"]
+           "streamlines.cpp", "glyph_kernels.hip", "glyphs.cpp", "block_stream_kernels.hip",
+           "block_streamlines.cpp"]
 HEADERS = ["rt_common.h", "rt_device.h", "shade_device.h", "cam_device.h", "rt_kernels.h", "rt_ctx.h",
            "bvh_build.h", "scene_host.h", "insitu_kernels.h", "footprint.h", "refit_common.h",
            "refit_kernels.h", "build_common.h", "build_kernels.h", "iso_common.h",
            "iso_kernels.h", "job_arena.h", "block_scan.h", "color_common.h", "tet_common.h",
            "tet_kernels.h", "tet_pipeline.h", "cell_common.h", "cell_kernels.h",
            "surf_common.h", "surf_kernels.h", "clip_common.h", "clip_kernels.h",
-           "stream_common.h", "stream_kernels.h", "glyph_common.h", "glyph_kernels.h"]
+           "stream_common.h", "stream_kernels.h", "glyph_common.h", "glyph_kernels.h",
+           "stream_host.h", "block_stream_common.h", "block_stream_kernels.h"]
 PUBLIC = [os.path.join(ROOT, "include", h) for h in ("spray_rt.h", "spray_scene.h")]
 
 

@@ -413,7 +413,7 @@ int spray_rt_destroy(spray_rt_ctx_t c) {
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (JobArena* a : {&c->refit, &c->build, &c->iso, &c->recolor, &c->tet, &c->cell, &c->surf,
-                      &c->clip, &c->stream, &c->glyph})
+                      &c->clip, &c->stream, &c->glyph, &c->bstream})
     arena_release(a);
   if (c->recolor_copied) (void)hipEventDestroy(c->recolor_copied);
   for (hipEvent_t e : c->tet_ev)

@@ -115,6 +115,8 @@ struct spray_rt_ctx {
   double stream_ms[3] = {};           // spray_rt_stream_phase_times
   spray_rt::detail::JobArena glyph;  // glyphs: job tables, counts | sphere tables, staged arrays, per-point scratch
   double glyph_ms[3] = {};           // spray_rt_glyph_phase_times
+  spray_rt::detail::JobArena bstream;  // block streamlines: job and block tables, records | staged arrays, per-lane scratch
+  double bstream_ms[3] = {};           // spray_rt_block_stream_phase_times
   double* d_sah = nullptr;  // spray_rt_slot_sah's result
   void* d_sort = nullptr;  // device build: temporary storage of the segmented sort
   size_t sort_cap = 0;

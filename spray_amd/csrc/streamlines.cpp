@@ -22,52 +22,24 @@
 
 #include "color_common.h"
 #include "rt_common.h"
+#ifndef SPRAY_RT_STREAM_HOST_ONLY
 #include "rt_ctx.h"
+#endif
 #include "spray_rt.h"
 #include "stream_common.h"
+#include "stream_host.h"
 #include "stream_kernels.h"
 
 using namespace spray_rt;
 using namespace spray_rt::detail;
+using namespace spray_rt::strmhost;
 
-namespace {
+namespace spray_rt {
+namespace strmhost {
 
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
-}
-
-constexpr uint64_t kMaxGridPoints = uint64_t(1) << 31;
-constexpr uint64_t kMaxSeeds = uint64_t(1) << 31;
 constexpr uint64_t kMaxLinePoints = uint64_t(1) << 32;
 constexpr uint64_t kMaxVerts = uint64_t(1) << 32;
 constexpr uint64_t kMaxFaces = uint64_t(1) << 29;
-
-// What is wrong with a field's description (nullptr: nothing); *code = the error.
-const char* field_error(const spray_rt_vecfield& f, int* code) {
-  *code = SPRAY_RT_ERR_ARG;
-  if (!f.vectors) return "null vectors";
-  if (f.nseeds && !f.seeds) return "null seeds";
-  for (int a = 0; a < 3; ++a) {
-    if (f.dims[a] < 2) return "fewer than 2 points on an axis";
-    if (!(f.spacing[a] > 0.0f) || !refit::finite_f(f.spacing[a]))
-      return "spacing is not positive and finite";
-    if (!refit::finite_f(f.origin[a])) return "non-finite origin";
-  }
-  if (!(f.step > 0.0f) || !refit::finite_f(f.step)) return "step is not positive and finite";
-  if (f.max_steps < 0 || f.max_steps > strm::kMaxSteps) return "max_steps is not in 0 .. 65535";
-  if (f.direction < SPRAY_RT_STREAM_FORWARD || f.direction > SPRAY_RT_STREAM_BOTH)
-    return "bad direction";
-  const float msq = f.min_speed * f.min_speed;
-  if (!(f.min_speed > 0.0f) || !refit::finite_f(msq) || !(msq >= 1.17549435e-38f))
-    return "min_speed is not positive with a normal square";
-  *code = SPRAY_RT_ERR_LIMIT;
-  if (uint64_t(f.dims[0]) * uint64_t(f.dims[1]) * uint64_t(f.dims[2]) >= kMaxGridPoints)
-    return "2^31 or more points";
-  if (uint64_t(f.nseeds) >= kMaxSeeds) return "2^31 or more seeds";
-  *code = SPRAY_RT_OK;
-  return nullptr;
-}
 
 const char* tube_error(const spray_rt_tube& t) {
   if (!(t.radius > 0.0f) || !refit::finite_f(t.radius)) return "radius is not positive and finite";
@@ -75,21 +47,6 @@ const char* tube_error(const spray_rt_tube& t) {
   return nullptr;
 }
 
-// ... with a field's colour map; a field without a colour field has none.
-const char* color_error(const spray_rt_grid_color* gc, float* scale) {
-  *scale = 0.0f;
-  if (!gc || !gc->field) return nullptr;
-  if (!gc->table_rgb) return "null colour table";
-  if (gc->ntable < 1 || gc->ntable > cmap::kMaxTable)
-    return "colour table of fewer than 1 or more than 4096 entries";
-  if (!refit::finite_f(gc->lo) || !refit::finite_f(gc->hi) || !(gc->lo < gc->hi))
-    return "colour range is not lo < hi, both finite";
-  if (!cmap::map_scale(gc->ntable, gc->lo, gc->hi, scale))
-    return "colour scale ntable / (hi - lo) is not a finite normal float";
-  return nullptr;
-}
-
-// What is wrong with a field's totals (nullptr: nothing).
 const char* totals_error(uint64_t npoints, uint64_t nverts, uint64_t nfaces) {
   if (npoints >= kMaxLinePoints) return "2^32 or more points of lines";
   if (nverts >= kMaxVerts) return "2^32 or more vertices";
@@ -105,6 +62,129 @@ void ring_table(int nsides, float out[][2]) {
   }
 }
 
+const char* color_table_error(const uint32_t* table_rgb, int32_t ntable, float lo, float hi,
+                              float* scale) {
+  *scale = 0.0f;
+  if (!table_rgb) return "null colour table";
+  if (ntable < 1 || ntable > cmap::kMaxTable)
+    return "colour table of fewer than 1 or more than 4096 entries";
+  if (!refit::finite_f(lo) || !refit::finite_f(hi) || !(lo < hi))
+    return "colour range is not lo < hi, both finite";
+  if (!cmap::map_scale(ntable, lo, hi, scale))
+    return "colour scale ntable / (hi - lo) is not a finite normal float";
+  return nullptr;
+}
+
+const char* trace_error(float step, int32_t max_steps, int32_t direction, float min_speed) {
+  if (!(step > 0.0f) || !refit::finite_f(step)) return "step is not positive and finite";
+  if (max_steps < 0 || max_steps > strm::kMaxSteps) return "max_steps is not in 0 .. 65535";
+  if (direction < SPRAY_RT_STREAM_FORWARD || direction > SPRAY_RT_STREAM_BOTH)
+    return "bad direction";
+  const float msq = min_speed * min_speed;
+  if (!(min_speed > 0.0f) || !refit::finite_f(msq) || !(msq >= 1.17549435e-38f))
+    return "min_speed is not positive with a normal square";
+  return nullptr;
+}
+
+void tubes_host(const HostLines& L, const spray_rt_tube& tube, float* verts_out,
+                float* vnormals_out, uint32_t* colors_out, uint32_t* faces_out) {
+  const uint32_t ns = uint32_t(tube.nsides);
+  float ring[strm::kMaxSides][2];
+  ring_table(tube.nsides, ring);
+  size_t v0 = 0, f0 = 0;
+  for (size_t l = 0; l + 1 < L.off.size(); ++l) {
+    const size_t p0 = L.off[l];
+    const uint32_t m = L.off[l + 1] - L.off[l];
+    if (m < 2) continue;
+    for (uint32_t r = 0; r < uint32_t(strm::tube_verts(m, ns)); ++r) {
+      const bool is_ring = r < m * ns;
+      const uint32_t j = is_ring ? r / ns : (r == m * ns ? 0u : m - 1), k = is_ring ? r - j * ns : 0u;
+      const float *P = &L.P[3 * (p0 + j)], *N = &L.N[3 * (p0 + j)], *T = &L.T[3 * (p0 + j)];
+      float pos[3], nrm[3];
+      if (is_ring) {
+        float B[3];
+        strm::cross3(T, N, B);
+        strm::ring_vertex(P, N, B, ring[k][0], ring[k][1], tube.radius, pos, nrm);
+      } else {
+        for (int a = 0; a < 3; ++a) {
+          pos[a] = P[a];
+          nrm[a] = j ? T[a] : -T[a];
+        }
+      }
+      for (int a = 0; a < 3; ++a) {
+        if (verts_out) verts_out[3 * (v0 + r) + size_t(a)] = pos[a];
+        if (vnormals_out) vnormals_out[3 * (v0 + r) + size_t(a)] = nrm[a];
+      }
+      if (colors_out) colors_out[v0 + r] = L.col[p0 + j];
+    }
+    for (uint32_t r = 0; faces_out && r < uint32_t(strm::tube_faces(m, ns)); ++r) {
+      uint32_t f[3];
+      strm::tube_face(ns, m, r, f);
+      for (int a = 0; a < 3; ++a) faces_out[3 * (f0 + r) + size_t(a)] = uint32_t(v0) + f[a];
+    }
+    v0 += size_t(strm::tube_verts(m, ns));
+    f0 += size_t(strm::tube_faces(m, ns));
+  }
+}
+
+void take_tube_scratch(Layout* M, size_t nseeds, const StreamRec& rec, TubeScratch* t) {
+  const size_t np = size_t(rec.npoints);
+  t->points = M->take<float>(3 * np);
+  t->pnormals = M->take<float>(3 * np);
+  t->ptangents = M->take<float>(3 * np);
+  t->pcolors = M->take<uint32_t>(np);
+  t->line_offsets = M->take<uint32_t>(nseeds + 1);
+  t->tube_points = M->take<uint32_t>(nseeds + 1);
+  t->tube_lines = M->take<uint32_t>(nseeds + 1);
+}
+void set_tube_scratch(StreamOut* O, const TubeScratch& t, void* base, const StreamRec& rec) {
+  O->points = t.points.at(base);
+  O->pnormals = t.pnormals.at(base);
+  O->ptangents = t.ptangents.at(base);
+  O->pcolors = t.pcolors.at(base);
+  O->line_offsets = t.line_offsets.at(base);
+  O->tube_points = t.tube_points.at(base);
+  O->tube_lines = t.tube_lines.at(base);
+  O->cap_points = rec.npoints;
+}
+
+}  // namespace strmhost
+}  // namespace spray_rt
+
+namespace {
+
+using Clock = std::chrono::steady_clock;
+double ms_since(Clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+}
+
+// What is wrong with a field's description (nullptr: nothing); *code = the error.
+const char* field_error(const spray_rt_vecfield& f, int* code) {
+  *code = SPRAY_RT_ERR_ARG;
+  if (!f.vectors) return "null vectors";
+  if (f.nseeds && !f.seeds) return "null seeds";
+  for (int a = 0; a < 3; ++a) {
+    if (f.dims[a] < 2) return "fewer than 2 points on an axis";
+    if (!(f.spacing[a] > 0.0f) || !refit::finite_f(f.spacing[a]))
+      return "spacing is not positive and finite";
+    if (!refit::finite_f(f.origin[a])) return "non-finite origin";
+  }
+  if (const char* why = trace_error(f.step, f.max_steps, f.direction, f.min_speed)) return why;
+  *code = SPRAY_RT_ERR_LIMIT;
+  if (uint64_t(f.dims[0]) * uint64_t(f.dims[1]) * uint64_t(f.dims[2]) >= kMaxGridPoints)
+    return "2^31 or more points";
+  if (uint64_t(f.nseeds) >= kMaxSeeds) return "2^31 or more seeds";
+  *code = SPRAY_RT_OK;
+  return nullptr;
+}
+
+// ... with a field's colour map; a field without a colour field has none.
+const char* color_error(const spray_rt_grid_color* gc, float* scale) {
+  *scale = 0.0f;
+  if (!gc || !gc->field) return nullptr;
+  return color_table_error(gc->table_rgb, gc->ntable, gc->lo, gc->hi, scale);
+}
+
 strm::Grid grid_of(const spray_rt_vecfield& f) {
   strm::Grid G;
   G.vectors = f.vectors;
@@ -117,12 +197,6 @@ strm::Grid grid_of(const spray_rt_vecfield& f) {
 }
 
 // ---- the host restatement, step for step what the kernels do ----
-
-struct HostLines {
-  std::vector<float> P, N, T;
-  std::vector<uint32_t> col, off, info;
-  uint64_t npoints = 0, tube_points = 0, tube_lines = 0;
-};
 
 struct Half {
   std::vector<float> P, N, T;
@@ -220,6 +294,7 @@ void lines_host(const spray_rt_vecfield& F, const spray_rt_grid_color* gc, float
   if (emit) L->off.push_back(uint32_t(L->npoints));
 }
 
+#ifndef SPRAY_RT_STREAM_HOST_ONLY
 // ---- the device extraction: check, count, the host read, integrate, expand ----
 
 struct StreamCall {
@@ -393,34 +468,7 @@ int stream_emit(spray_rt_ctx* c, int n, const StreamCall& call, const std::vecto
   }
   return SPRAY_RT_OK;
 }
-
-// The per-point and per-line scratch of the tube forms, laid out in M (of
-// d_isomesh) for the counted fields.
-struct TubeScratch {
-  Take<float> points, pnormals, ptangents;
-  Take<uint32_t> pcolors, line_offsets, tube_points, tube_lines;
-};
-void take_tube_scratch(Layout* M, const spray_rt_vecfield& f, const StreamRec& rec,
-                       TubeScratch* t) {
-  const size_t np = size_t(rec.npoints);
-  t->points = M->take<float>(3 * np);
-  t->pnormals = M->take<float>(3 * np);
-  t->ptangents = M->take<float>(3 * np);
-  t->pcolors = M->take<uint32_t>(np);
-  t->line_offsets = M->take<uint32_t>(f.nseeds + 1);
-  t->tube_points = M->take<uint32_t>(f.nseeds + 1);
-  t->tube_lines = M->take<uint32_t>(f.nseeds + 1);
-}
-void set_tube_scratch(StreamOut* O, const TubeScratch& t, void* base, const StreamRec& rec) {
-  O->points = t.points.at(base);
-  O->pnormals = t.pnormals.at(base);
-  O->ptangents = t.ptangents.at(base);
-  O->pcolors = t.pcolors.at(base);
-  O->line_offsets = t.line_offsets.at(base);
-  O->tube_points = t.tube_points.at(base);
-  O->tube_lines = t.tube_lines.at(base);
-  O->cap_points = rec.npoints;
-}
+#endif  // SPRAY_RT_STREAM_HOST_ONLY
 
 }  // namespace
 
@@ -469,45 +517,11 @@ int spray_rt_stream_tubes_host(const spray_rt_vecfield* field, const spray_rt_tu
   if (nfaces) *nfaces = size_t(nf);
   if (totals_error(L.npoints, nv, nf)) return SPRAY_RT_ERR_LIMIT;
   if (!emit) return SPRAY_RT_OK;
-  float ring[strm::kMaxSides][2];
-  ring_table(tube->nsides, ring);
-  size_t v0 = 0, f0 = 0;
-  for (size_t l = 0; l + 1 < L.off.size(); ++l) {
-    const size_t p0 = L.off[l];
-    const uint32_t m = L.off[l + 1] - L.off[l];
-    if (m < 2) continue;
-    for (uint32_t r = 0; r < uint32_t(strm::tube_verts(m, ns)); ++r) {
-      const bool is_ring = r < m * ns;
-      const uint32_t j = is_ring ? r / ns : (r == m * ns ? 0u : m - 1), k = is_ring ? r - j * ns : 0u;
-      const float *P = &L.P[3 * (p0 + j)], *N = &L.N[3 * (p0 + j)], *T = &L.T[3 * (p0 + j)];
-      float pos[3], nrm[3];
-      if (is_ring) {
-        float B[3];
-        strm::cross3(T, N, B);
-        strm::ring_vertex(P, N, B, ring[k][0], ring[k][1], tube->radius, pos, nrm);
-      } else {
-        for (int a = 0; a < 3; ++a) {
-          pos[a] = P[a];
-          nrm[a] = j ? T[a] : -T[a];
-        }
-      }
-      for (int a = 0; a < 3; ++a) {
-        if (verts_out) verts_out[3 * (v0 + r) + size_t(a)] = pos[a];
-        if (vnormals_out) vnormals_out[3 * (v0 + r) + size_t(a)] = nrm[a];
-      }
-      if (colors_out) colors_out[v0 + r] = L.col[p0 + j];
-    }
-    for (uint32_t r = 0; faces_out && r < uint32_t(strm::tube_faces(m, ns)); ++r) {
-      uint32_t f[3];
-      strm::tube_face(ns, m, r, f);
-      for (int a = 0; a < 3; ++a) faces_out[3 * (f0 + r) + size_t(a)] = uint32_t(v0) + f[a];
-    }
-    v0 += size_t(strm::tube_verts(m, ns));
-    f0 += size_t(strm::tube_faces(m, ns));
-  }
+  tubes_host(L, *tube, verts_out, vnormals_out, colors_out, faces_out);
   return SPRAY_RT_OK;
 }
 
+#ifndef SPRAY_RT_STREAM_HOST_ONLY
 int spray_rt_stream_phase_times(spray_rt_ctx_t c, double out_ms[3]) {
   if (!c || !out_ms) return SPRAY_RT_ERR_ARG;
   for (int k = 0; k < 3; ++k) out_ms[k] = c->stream_ms[k];
@@ -595,7 +609,7 @@ int spray_rt_stream_tubes(spray_rt_ctx_t c, int n, const spray_rt_vecfield* fiel
   if (!any) return SPRAY_RT_OK;
   Layout M;  // of d_isomesh
   std::vector<TubeScratch> ts(nj);
-  for (size_t k = 0; k < nj; ++k) take_tube_scratch(&M, fields[k], call.rec[k], &ts[k]);
+  for (size_t k = 0; k < nj; ++k) take_tube_scratch(&M, fields[k].nseeds, call.rec[k], &ts[k]);
   const int g = ensure(c, &c->d_isomesh, &c->isomesh_cap, std::max<size_t>(M.used, 256));
   if (g) return g;
   for (size_t k = 0; k < nj; ++k) set_tube_scratch(&outs[k], ts[k], c->d_isomesh, call.rec[k]);
@@ -639,7 +653,7 @@ int spray_rt_domains_stream_tubes(spray_rt_ctx_t c, int n, const int* slots,
   std::vector<Take<uint32_t>> t_colors(nj), t_faces(nj);
   std::vector<size_t> nv(nj), nf(nj);
   for (size_t k = 0; k < nj; ++k) {
-    take_tube_scratch(&M, fields[k], call.rec[k], &ts[k]);
+    take_tube_scratch(&M, fields[k].nseeds, call.rec[k], &ts[k]);
     outs[k].cap_verts = nv[k] = size_t(call.nverts[k]);
     outs[k].cap_faces = nf[k] = size_t(call.nfaces[k]);
     t_verts[k] = M.take<float>(3 * nv[k]);
@@ -680,5 +694,6 @@ int spray_rt_domains_stream_tubes(spray_rt_ctx_t c, int n, const int* slots,
   c->stream_ms[2] = ms_since(t2);
   return SPRAY_RT_OK;
 }
+#endif  // SPRAY_RT_STREAM_HOST_ONLY
 
 }  // extern "C"

@@ -20,6 +20,7 @@ __all__ = ["RtContext", "Scene", "OocCache", "ooc_scene", "camera_init", "make_r
            "isosurface_mapped_host", "colormap_host", "tet_isosurface_host",
            "cell_isosurface_host", "cell_split_host", "cell_surface_host", "cell_clip_host",
            "plane_values_host", "streamlines_host", "stream_tubes_host", "tube_ring",
+           "block_streamlines_host", "block_stream_tubes_host",
            "STREAM_FORWARD", "STREAM_BACKWARD", "STREAM_BOTH", "LINE_END_GRID", "LINE_END_STEPS",
            "LINE_END_SPEED", "LINE_END_SEED", "glyphs_host", "glyph_sphere", "GLYPH_SPHERE",
            "GLYPH_ARROW", "SLOT_COLORS",
@@ -792,6 +793,136 @@ def tube_ring(nsides):
         e.code = rc
         raise e
     return out
+
+
+def _block_tables(sets, tubes=None):
+    """Dicts with the keys blocks (a list of dicts with vectors float32 [nz, ny,
+    nx, 3], origin, spacing and optionally cfield float32 [nz, ny, nx]), seeds
+    (float32 [nseeds, 3]), step, max_steps and optionally direction
+    (STREAM_FORWARD), min_speed (1e-6) and cmap = (table uint32[n], lo, hi) for
+    sets whose blocks have a cfield; arrays are numpy arrays or torch tensors on
+    the GPU.  tubes as in _stream_tables -> (spray_rt_blockfield array,
+    spray_rt_tube array or None, spray_rt_block_color array, keepalive)."""
+    from ._native import BlockColor, BlockField, Tube, VecBlock
+    m = max(len(sets), 1)
+    arr, carr = (BlockField * m)(), (BlockColor * m)()
+    keep = []
+    for f, rec, crec in zip(sets, arr, carr):
+        blocks = list(f["blocks"])
+        barr = (VecBlock * max(len(blocks), 1))()
+        keep.append(barr)
+        for b, brec in zip(blocks, barr):
+            vec = _float_array(b["vectors"], "vectors", (3,))
+            if len(vec.shape) != 4:
+                raise ValueError("streamlines: vectors are a [nz, ny, nx, 3] array")
+            keep.append(vec)
+            brec.vectors = _addr(vec)[0]
+            nz, ny, nx = (int(d) for d in vec.shape[:3])
+            brec.dims = (C.c_int32 * 3)(nx, ny, nz)
+            brec.origin = (C.c_float * 3)(*[float(x) for x in b["origin"]])
+            brec.spacing = (C.c_float * 3)(*[float(x) for x in b["spacing"]])
+            cf = b.get("cfield")
+            if cf is not None:
+                cf = _float_array(cf, "colour fields", ())
+                if tuple(cf.shape) != tuple(vec.shape[:3]):
+                    raise ValueError("streamlines: a colour field has its grid's shape")
+                keep.append(cf)
+                brec.color_field = _addr(cf)[0]
+        seeds = _float_array(f["seeds"], "seeds", (3,))
+        nseeds = int(np.prod(seeds.shape[:-1])) if len(seeds.shape) > 1 else 1
+        keep.append(seeds)
+        rec.blocks = C.addressof(barr) if blocks else None
+        rec.nblocks = len(blocks)
+        rec.seeds = _addr(seeds)[0] if nseeds else None
+        rec.nseeds = nseeds
+        rec.step = float(f["step"])
+        rec.max_steps = int(f["max_steps"])
+        rec.direction = int(f.get("direction", STREAM_FORWARD))
+        rec.min_speed = float(f.get("min_speed", 1e-6))
+        if f.get("cmap") is not None:
+            t, crec.table_rgb, crec.ntable, crec.lo, crec.hi = _cmap_args(f["cmap"])
+            keep.append(t)
+    tarr = None
+    if tubes is not None:
+        if isinstance(tubes, dict):
+            tubes = [tubes] * len(sets)
+        if len(tubes) != len(sets):
+            raise ValueError("block_stream_tubes: one tube per set")
+        tarr = (Tube * m)()
+        for t, rec in zip(tubes, tarr):
+            rec.radius = float(t["radius"])
+            rec.nsides = int(t["nsides"])
+            color = t.get("color")
+            rec.has_color = 0 if color is None else 1
+            rec.color_rgb = 0 if color is None else int(color)
+    return arr, tarr, carr, keep
+
+
+def _block_set(blocks, seeds, step, max_steps, direction, min_speed, cmap=None):
+    bl = [dict(b, vectors=np.ascontiguousarray(b["vectors"], np.float32)) for b in blocks]
+    return dict(blocks=bl, seeds=np.ascontiguousarray(seeds, np.float32).reshape(-1, 3),
+                step=step, max_steps=max_steps, direction=direction, min_speed=min_speed,
+                cmap=cmap)
+
+
+def block_streamlines_host(blocks, seeds, step, max_steps, direction=STREAM_FORWARD,
+                           min_speed=1e-6):
+    """spray_rt_block_streamlines_host (no GPU): the polylines
+    RtContext.block_streamlines traces through a set of blocks (see
+    _block_tables) -> (points float32 [np, 3], line_offsets uint32 [nseeds + 1],
+    line_info uint32 [nseeds, 2], point_blocks uint32 [np])."""
+    f = _block_set(blocks, seeds, step, max_steps, direction, min_speed)
+    arr, _, _, keep = _block_tables([f])
+    L = lib()
+    npts = C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_block_streamlines_host(C.addressof(arr), C.byref(npts), *outs)
+        if rc != 0:
+            e = SprayRtError("block_streamlines_host failed (%d)" % rc)
+            e.code = rc
+            e.counts = npts.value
+            raise e
+
+    call(None, None, None, None)
+    ns = int(arr[0].nseeds)
+    p = np.zeros((npts.value, 3), np.float32)
+    off = np.zeros(ns + 1, np.uint32)
+    info = np.zeros((ns, 2), np.uint32)
+    blk = np.zeros(npts.value, np.uint32)
+    call(p.ctypes.data, off.ctypes.data, info.ctypes.data, blk.ctypes.data)
+    return p, off, info, blk
+
+
+def block_stream_tubes_host(blocks, seeds, step, max_steps, radius, nsides,
+                            direction=STREAM_FORWARD, min_speed=1e-6, color=None, cmap=None,
+                            normals=True, count_only=False):
+    """spray_rt_block_stream_tubes_host (no GPU): the tube mesh
+    RtContext.block_stream_tubes builds, as stream_tubes_host."""
+    f = _block_set(blocks, seeds, step, max_steps, direction, min_speed, cmap)
+    arr, tarr, carr, keep = _block_tables([f], dict(radius=radius, nsides=nsides, color=color))
+    L = lib()
+    nv, nf = C.c_size_t(), C.c_size_t()
+
+    def call(*outs):
+        rc = L.spray_rt_block_stream_tubes_host(C.addressof(arr), C.addressof(tarr),
+                                                C.addressof(carr), C.byref(nv), C.byref(nf),
+                                                *outs)
+        if rc != 0:
+            e = SprayRtError("block_stream_tubes_host failed (%d)" % rc)
+            e.code = rc
+            e.counts = (nv.value, nf.value)
+            raise e
+
+    call(None, None, None, None)
+    if count_only:
+        return nv.value, nf.value
+    v = np.zeros((nv.value, 3), np.float32)
+    n = np.zeros((nv.value, 3), np.float32) if normals else None
+    c = np.zeros(nv.value, np.uint32)
+    fc = np.zeros((nf.value, 3), np.uint32)
+    call(v.ctypes.data, None if n is None else n.ctypes.data, c.ctypes.data, fc.ctypes.data)
+    return v, n, c, fc
 
 
 GLYPH_SPHERE, GLYPH_ARROW = 0, 1
@@ -1815,6 +1946,120 @@ class RtContext:
         ms of the device build]."""
         out = (C.c_double * 3)()
         self._check(lib().spray_rt_stream_phase_times(self.h, out), "stream_phase_times")
+        return list(out)
+
+    # ---- streamlines across blocks ----
+    def block_streamlines(self, sets, capacity=None, count_only=False):
+        """spray_rt_block_streamlines: the streamlines through sets of vector
+        blocks (see _block_tables) in one batched call -> [(points, line_offsets,
+        line_info, point_blocks int32 [np] holding the uint32 bits)], the first
+        three and capacity / count_only as in streamlines."""
+        import torch
+        n = len(sets)
+        arr, _, _, keep = _block_tables(sets)
+        m = max(n, 1)
+        npts = (C.c_size_t * m)()
+        fn = lib().spray_rt_block_streamlines
+        if capacity is None or count_only:
+            self._check(fn(self.h, n, arr, None, None, None, None, None, npts),
+                        "block_streamlines")
+            if count_only:
+                return [npts[i] for i in range(n)]
+            caps = [npts[i] for i in range(n)]
+        else:
+            caps = [int(capacity)] * n
+        dev = "cuda:%d" % self._device
+        # zeroed, one element at least: a buffer a failed call must not touch
+        p = [torch.zeros((max(c, 1), 3), dtype=torch.float32, device=dev) for c in caps]
+        off = [torch.zeros(int(arr[i].nseeds) + 1, dtype=torch.int32, device=dev)
+               for i in range(n)]
+        info = [torch.zeros((max(int(arr[i].nseeds), 1), 2), dtype=torch.int32, device=dev)
+                for i in range(n)]
+        blk = [torch.zeros(max(c, 1), dtype=torch.int32, device=dev) for c in caps]
+        ptrs = lambda xs: (C.c_void_p * m)(*[x.data_ptr() for x in xs])
+        _fills_done()
+        try:
+            self._check(fn(self.h, n, arr, ptrs(p), ptrs(off), ptrs(info), ptrs(blk),
+                           (C.c_size_t * m)(*caps), npts), "block_streamlines")
+        except SprayRtError as e:
+            e.counts = [npts[i] for i in range(n)]
+            e.buffers = (p, off, info, blk)
+            raise
+        return [(p[i][:npts[i]], off[i], info[i][:int(arr[i].nseeds)], blk[i][:npts[i]])
+                for i in range(n)]
+
+    def block_stream_tubes(self, sets, tubes, normals=True, capacity=None, count_only=False):
+        """spray_rt_block_stream_tubes: the streamlines through sets of blocks as
+        tubes (see _block_tables); results, capacity and count_only as in
+        stream_tubes."""
+        import torch
+        n = len(sets)
+        arr, tarr, carr, keep = _block_tables(sets, tubes)
+        m = max(n, 1)
+        nv, nf = (C.c_size_t * m)(), (C.c_size_t * m)()
+        fn = lib().spray_rt_block_stream_tubes
+        if capacity is None or count_only:
+            self._check(fn(self.h, n, arr, tarr, carr, None, None, None, None, None, None, nv, nf),
+                        "block_stream_tubes")
+            if count_only:
+                return [(nv[i], nf[i]) for i in range(n)]
+            caps = [(nv[i], nf[i]) for i in range(n)]
+        else:
+            caps = [(int(capacity[0]), int(capacity[1]))] * n
+        dev = "cuda:%d" % self._device
+        # zeroed, one element at least: a buffer a failed call must not touch
+        v = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) for cv, _ in caps]
+        nr = [torch.zeros((max(cv, 1), 3), dtype=torch.float32, device=dev) if normals else None
+              for cv, _ in caps]
+        col = [torch.zeros(max(cv, 1), dtype=torch.int32, device=dev) for cv, _ in caps]
+        f = [torch.zeros((max(cf, 1), 3), dtype=torch.int32, device=dev) for _, cf in caps]
+        ptrs = lambda xs: (C.c_void_p * m)(*[None if x is None else x.data_ptr() for x in xs])
+        _fills_done()
+        try:
+            self._check(fn(self.h, n, arr, tarr, carr, ptrs(v), ptrs(nr) if normals else None,
+                           ptrs(col), ptrs(f), (C.c_size_t * m)(*[c[0] for c in caps]),
+                           (C.c_size_t * m)(*[c[1] for c in caps]), nv, nf),
+                        "block_stream_tubes")
+        except SprayRtError as e:
+            e.counts = [(nv[i], nf[i]) for i in range(n)]
+            e.buffers = tuple(b for b in (v, nr, col, f) if n and b[0] is not None)
+            raise
+        return [(v[i][:nv[i]], nr[i][:nv[i]] if normals else None, col[i][:nv[i]], f[i][:nf[i]])
+                for i in range(n)]
+
+    def block_stream_tubes_domains(self, slots, sets, tubes, normals=True, bounds=None):
+        """spray_rt_domains_block_stream_tubes: the tubes of block_stream_tubes()
+        into slots, a whole set's tubes into one slot; a slot carries colours
+        when its set's blocks have a cfield or its tube a color.  bounds as in
+        refit_domains -> (bounds result, triangle counts)."""
+        slots = [int(s) for s in slots]
+        n = len(slots)
+        if len(sets) != n:
+            e = SprayRtError("block_stream_tubes_domains: %d slots, %d sets" % (n, len(sets)))
+            e.code = -1
+            raise e
+        arr, tarr, carr, keep = _block_tables(sets, tubes)
+        m = max(n, 1)
+        sl = (C.c_int * m)(*slots)
+        out = self._bounds_out(bounds, n)
+        b, k = _addr(out)
+        nf = (C.c_size_t * m)()
+        self._check(lib().spray_rt_domains_block_stream_tubes(
+            self.h, n, sl, arr, tarr, carr, 1 if normals else 0, b, nf),
+            "domains_block_stream_tubes")
+        for s in slots:
+            self._nverts.pop(s, None)  # the vertex count is the expansion's
+        if bounds is True:
+            self.sync()
+            out = out[:n].cpu().numpy()
+        return out, [nf[i] for i in range(n)]
+
+    def block_stream_phase_times(self):
+        """spray_rt_block_stream_phase_times of the last block streamline call,
+        as stream_phase_times."""
+        out = (C.c_double * 3)()
+        self._check(lib().spray_rt_block_stream_phase_times(self.h, out),
+                    "block_stream_phase_times")
         return list(out)
 
     # ---- glyphs ----
