@@ -395,6 +395,11 @@ int block_count(spray_rt_ctx* c, const char* what, int n, const spray_rt_blockfi
   for (int i = 0; i < n; ++i) {
     const uint32_t st = h_status[2 * i];
     const int bad_block = h_status[2 * i + 1] == bstrm::kNoBlock ? -1 : int(h_status[2 * i + 1]);
+    // the block named is the lowest with a bad sample of either kind
+    if ((st & strm::kBadVector) && (st & strm::kBadColor))
+      return fail(c, SPRAY_RT_ERR_ARG,
+                  "%s: non-finite vector sample or sample of the colour field (the lowest such block)",
+                  name(i, bad_block).c_str());
     if (st & strm::kBadVector)
       return fail(c, SPRAY_RT_ERR_ARG, "%s: non-finite vector sample", name(i, bad_block).c_str());
     if (st & strm::kBadColor)

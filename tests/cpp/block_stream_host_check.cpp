@@ -11,15 +11,26 @@
 //
 // Every array is allocated at exactly the size the count call reports, so a
 // store or a read past an end is the sanitizer's to find.
+//
+// Then the box of the miss path by brute force (block_stream_common.h): for the
+// spacings, sizes and origins of the hard-box class of tests/block_stream_cases.py,
+// inside(box_of(R), p) against strm::locate(grid_of(R), p) for every float p
+// within 256 floats of either bound on each axis and for 2^20 floats spread over
+// the whole float line on each axis with a spacing of its own, the bounds themselves against the division, and the
+// float keys there and back.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
+#include "block_stream_common.h"
 #include "spray_rt.h"
 
 namespace {
+
+namespace bstrm = spray_rt::bstrm;
+namespace strm = spray_rt::strm;
 
 int failures = 0;
 void expect(bool ok, const char* what) {
@@ -88,6 +99,93 @@ std::vector<float> swirl(int n, float c) {
         s[2] = 0.0625f * float(std::sin(0.5 * double(i + k)));
       }
   return v;
+}
+
+// ---- the box of the miss path ----
+
+size_t box_checked = 0;
+
+// p on axis a, the origin on the other two (d = 0 there: inside).
+bool box_agrees(const bstrm::BlockRec& R, const bstrm::BlockBox& B, const strm::Grid& G, int a,
+                float x) {
+  float p[3] = {R.origin[0], R.origin[1], R.origin[2]};
+  p[a] = x;
+  strm::Cell c;
+  ++box_checked;
+  return bstrm::inside(B, p) == strm::locate(G, p, &c);
+}
+
+void check_box(const float spacing[3], int n, float origin, bool sweep) {
+  bstrm::BlockRec R{};
+  for (int a = 0; a < 3; ++a) {
+    R.origin[a] = origin;
+    R.spacing[a] = spacing[a];
+    R.n[a] = n;
+  }
+  const bstrm::BlockBox B = bstrm::box_of(R);
+  const strm::Grid G = bstrm::grid_of(R);
+  for (int a = 0; a < 3; ++a) {
+    const float s = spacing[a], top = float(n - 1);
+    // the bounds are the outermost floats whose quotient is in range
+    const uint32_t klo = bstrm::float_key(B.lo[a]), khi = bstrm::float_key(B.hi[a]);
+    expect(B.lo[a] / s >= 0.0f && !(bstrm::key_float(klo - 1) / s >= 0.0f), "lo is the lowest float in range");
+    expect(B.hi[a] / s <= top && !(bstrm::key_float(khi + 1) / s <= top), "hi is the highest float in range");
+    expect(B.lo[a] <= -0.0f && B.hi[a] >= 0.0f, "both zeros are in range");
+    // every p within 256 floats of origin + lo and of origin + hi
+    bool ok = true;
+    for (float at : {origin + B.lo[a], origin + B.hi[a]}) {
+      if (!std::isfinite(at)) at = at > 0 ? 3.4028235e38f : -3.4028235e38f;
+      const uint32_t k0 = bstrm::float_key(at);
+      for (int64_t k = int64_t(k0) - 256; k <= int64_t(k0) + 256; ++k)
+        if (k >= 0 && k <= int64_t(0xFFFFFFFFu)) ok = ok && box_agrees(R, B, G, a, bstrm::key_float(uint32_t(k)));
+    }
+    expect(ok, "box and division agree within 256 floats of the bounds");
+    if (!sweep || (a > 0 && spacing[a] == spacing[0])) continue;  // equal spacings: equal axes
+    ok = true;
+    for (uint32_t j = 0; j < (1u << 20); ++j) {  // one key in every stratum of 4096
+      const uint32_t k = j * 4096u + (j * 2654435761u >> 20);
+      ok = ok && box_agrees(R, B, G, a, bstrm::key_float(k));
+    }
+    expect(ok, "box and division agree over the float line");
+  }
+}
+
+void check_boxes() {
+  const float third = 1.0f / 3.0f;
+  const float spacings[8][3] = {{0.1f, 0.1f, 0.1f}, {third, third, third}, {0.7f, 0.7f, 0.7f},
+                                {3e-5f, 3e-5f, 3e-5f}, {1e-38f, 1e-38f, 1e-38f},
+                                {3e37f, 3e37f, 3e37f}, {0.1f, third, 0.7f}, {3e-5f, 0.7f, 1e-38f}};
+  const float origins[5] = {0.0f, -0.0f, 1e6f, -123456.7f, 1e-30f};
+  for (int s = 0; s < 8; ++s)
+    for (int o = 0; o < 5; ++o)
+      for (int n = 2; n <= 5; ++n) check_box(spacings[s], n, origins[o], n == 2 + (s + o) % 4);
+  // a spacing so small that hi is subnormal, one so large that top * s overflows
+  bstrm::BlockRec R{};
+  for (int a = 0; a < 3; ++a) R.spacing[a] = a == 0 ? 1e-38f : 3e38f, R.n[a] = 5;
+  const bstrm::BlockBox B = bstrm::box_of(R);
+  expect(B.hi[0] > 0.0f && B.hi[0] < 1.17549435e-38f * 4.0f && std::fpclassify(1e-38f) == FP_SUBNORMAL,
+         "a subnormal spacing has a tiny hi");
+  expect(B.hi[1] == 3.4028235e38f, "top * spacing overflows: every finite float is in range");
+  // the keys: order, and there and back bitwise
+  const float specials[] = {0.0f, -0.0f, strm::pos_inf(), -strm::pos_inf(), 1e-45f, -1e-45f,
+                            1.17549435e-38f, 3.4028235e38f, -3.4028235e38f, 1.0f, -1.0f, 0.1f};
+  for (float x : specials)
+    expect(strm::bits(bstrm::key_float(bstrm::float_key(x))) == strm::bits(x), "key there and back");
+  expect(bstrm::float_key(-0.0f) + 1 == bstrm::float_key(0.0f), "-0 is the float below +0");
+  expect(bstrm::float_key(-strm::pos_inf()) < bstrm::float_key(-3.4028235e38f) &&
+             bstrm::float_key(3.4028235e38f) + 1 == bstrm::float_key(strm::pos_inf()),
+         "the infinities are the ends of the finite floats");
+  bool ok = true;
+  uint32_t prev = 0;
+  for (uint32_t j = 0; j < (1u << 20); ++j) {
+    const uint32_t k = j * 4096u + (j * 2654435761u >> 20);
+    const float x = bstrm::key_float(k);
+    ok = ok && bstrm::float_key(x) == k;
+    if (j && x == x && bstrm::key_float(prev) == bstrm::key_float(prev))
+      ok = ok && bstrm::key_float(prev) <= x;  // the order of the keys is the order of the floats
+    prev = k;
+  }
+  expect(ok, "keys there and back and in order over the float line");
 }
 
 }  // namespace
@@ -203,6 +301,10 @@ int main() {
            "a colour table without colour fields");
   }
 
-  std::printf("block_stream_host_check: %zu crossings, %d failures\n", crossing, failures);
+  check_boxes();
+  expect(box_checked > (size_t(60) << 20), "the box sweep ran");
+
+  std::printf("block_stream_host_check: %zu crossings, %zu box tests, %d failures\n", crossing,
+              box_checked, failures);
   return failures ? 1 : 0;
 }

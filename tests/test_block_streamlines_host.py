@@ -156,7 +156,8 @@ def test_stand_alone_program_under_the_host_sanitizers(tmp_path):
     """tests/cpp/block_stream_host_check.cpp with the host restatements of
     streamlines.cpp and block_streamlines.cpp (SPRAY_RT_STREAM_HOST_ONLY:
     nothing that needs the HIP runtime), built by g++ under the address and
-    undefined-behaviour sanitizers and run as a plain executable."""
+    undefined-behaviour sanitizers and run as a plain executable.  It also
+    holds the box of the miss path to the division by brute force."""
     from spray_amd import build
     root = build.ROOT
     rocm = os.path.dirname(os.path.dirname(os.path.realpath(build.hipcc())))
