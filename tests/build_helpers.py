@@ -1,5 +1,6 @@
 """Meshes, numpy restatements and query checks shared by the device-build tests
-(test_build_host.py, test_gpu_build.py)."""
+(test_build_host.py, test_gpu_build.py, and test_build_cases.py and
+test_gpu_build_cases.py on the classes of build_cases.py)."""
 import numpy as np
 
 import refit_helpers as rh
@@ -94,6 +95,163 @@ def build_device_host(v, f):
     out["nodes"] = r["nodes"].reshape(-1).view(rh.NODE_DTYPE)
     out["qnodes4"] = r["qnodes4"].reshape(-1).view(rh.QNODE4_DTYPE)
     return out
+
+
+# ---- vectorised forms over the BFS levels (a million triangles in numpy) ----
+def level_ranges(child):
+    """[(first, end)] of the BFS levels of a tree numbered breadth first;
+    child [n, k]: the refs of every node, inner ones >= 0."""
+    inner = np.asarray(child) >= 0
+    out, b, e = [], 0, min(1, len(inner))
+    while b < e:
+        out.append((b, e))
+        b, e = e, e + int(inner[b:e].sum())
+    return out
+
+
+def level_widths(child):
+    return [e - b for b, e in level_ranges(child)]
+
+
+def carry_live(child, chunk=512):
+    """Whether some level wider than `chunk` has inner children both among its
+    first `chunk` nodes and after them: the numbering of the later ones then
+    depends on the count carried over from the first chunk."""
+    inner = np.asarray(child) >= 0
+    return any(e - b > chunk and inner[b:b + chunk].any() and inner[b + chunk:e].any()
+               for b, e in level_ranges(child))
+
+
+def node_refs(nodes):
+    return np.stack([nodes["left"], nodes["right"]], 1).astype(np.int64)
+
+
+def check_structure(nodes, ntris):
+    """test_build_host.test_tree_structure's checks without a loop over the
+    nodes: leaves of 1..4 triangles tile [0, ntris) once, every node but the
+    root is referred to once and after its parent, the numbering is breadth
+    first.  -> (depth per node, depth of the tree)."""
+    nn = len(nodes)
+    refs = node_refs(nodes)
+    live = np.stack([nodes["l_lo"][:, 0], nodes["r_lo"][:, 0]], 1) != np.inf
+    assert live[:, 0].all() and (live[:, 1].all() or nn == 1)
+    leaf = live & (refs < 0)
+    u = (~refs[leaf]) & 0xFFFFFFFF
+    first, cnt = np.sort(u >> 2), ((u & 3) + 1)[np.argsort(u >> 2, kind="stable")]
+    assert first[0] == 0 and np.array_equal(first[1:], (first + cnt)[:-1])
+    assert first[-1] + cnt[-1] == ntris and cnt.min() >= 1 and cnt.max() <= KLEAFMAX
+    inner = live & (refs >= 0)
+    assert np.array_equal(np.sort(refs[inner]), np.arange(1, nn))
+    assert (refs[inner] > np.nonzero(inner)[0]).all()
+    assert (nodes["pad"] == 0).all()
+    # breadth first: the inner refs of a level, in node order, are the next level
+    depth = np.zeros(nn, np.int64)
+    levels = level_ranges(np.where(live, refs, -1))
+    for d, (b, e) in enumerate(levels):
+        depth[b:e] = d
+        nxt = refs[b:e][inner[b:e]]
+        end = levels[d + 1][1] if d + 1 < len(levels) else e
+        assert np.array_equal(nxt, np.arange(e, end))
+    assert levels[-1][1] == nn
+    return depth, len(levels)
+
+
+def _leaf_fold(first, cnt, lo_t, hi_t):
+    """min / max over the triangles [first, first + cnt) of per-triangle boxes."""
+    lo, hi = lo_t[first].copy(), hi_t[first].copy()
+    for c in range(1, KLEAFMAX):
+        k = first + np.minimum(c, cnt - 1)
+        lo, hi = np.minimum(lo, lo_t[k]), np.maximum(hi, hi_t[k])
+    return lo, hi
+
+
+def tree_levels(refs, live):
+    """The nodes of every depth as index arrays, root first, for any numbering
+    (a breadth-first one gives consecutive ranges)."""
+    out, idx = [], np.arange(min(1, len(refs)))
+    while len(idx):
+        out.append(idx)
+        r = refs[idx]
+        idx = r[live[idx] & (r >= 0)]
+    return out
+
+
+def expected_boxes_by_level(nodes, prims, f, v):
+    """refit_helpers.expected_boxes bottom up, a level of the tree at a time:
+    (plo, phi, rng) of the same shapes and bytes."""
+    nn = len(nodes)
+    refs = node_refs(nodes)
+    live = np.stack([nodes["l_lo"][:, 0], nodes["r_lo"][:, 0]], 1) != np.inf
+    pts = v[f[prims]]                      # [nt, 3, 3]
+    lo_t, hi_t = pts.min(1), pts.max(1)
+    lo = np.stack([nodes["l_lo"], nodes["r_lo"]], 1).astype(F32)   # the never-hit box stays
+    hi = np.stack([nodes["l_hi"], nodes["r_hi"]], 1).astype(F32)
+    rng = np.full((nn, 2, 2), -1, np.int64)
+    for idx in tree_levels(refs, live)[::-1]:
+        for side in range(2):
+            r, lv = refs[idx, side], live[idx, side]
+            leaf, inner = lv & (r < 0), lv & (r >= 0)
+            u = (~r[leaf]) & 0xFFFFFFFF
+            first, cnt = u >> 2, (u & 3) + 1
+            lo[idx[leaf], side], hi[idx[leaf], side] = _leaf_fold(first, cnt, lo_t, hi_t)
+            rng[idx[leaf], side] = np.stack([first, first + cnt], 1)
+            c = r[inner]
+            lo[idx[inner], side] = np.minimum(lo[c, 0], lo[c, 1])
+            hi[idx[inner], side] = np.maximum(hi[c, 0], hi[c, 1])
+            rng[idx[inner], side] = np.stack([rng[c, 0, 0], rng[c, 1, 1]], 1)
+    plo, phi = rh.pad_np(lo, hi)
+    plo[~live], phi[~live] = lo[~live], hi[~live]
+    return plo, phi, rng
+
+
+def q4_ranges_by_level(q4):
+    """refit_helpers.q4_child_ranges bottom up, a level at a time."""
+    child = q4["child"].astype(np.int64)
+    rng = np.full((len(q4), 4, 2), -1, np.int64)
+    big = np.iinfo(np.int64).max
+    for idx in tree_levels(child, child != rh.KNOCHILD)[::-1]:
+        for c in range(4):
+            r = child[idx, c]
+            leaf, inner = (r < 0) & (r != rh.KNOCHILD), r >= 0
+            u = (~r[leaf]) & 0xFFFFFFFF
+            rng[idx[leaf], c] = np.stack([u >> 2, (u >> 2) + (u & 3) + 1], 1)
+            sub = rng[r[inner]]                # [k, 4, 2]
+            rng[idx[inner], c] = np.stack([np.where(sub[:, :, 0] >= 0, sub[:, :, 0], big).min(1),
+                                           sub[:, :, 1].max(1)], 1)
+    return rng
+
+
+def check_qnodes4(q4, grid, rng, plo, phi, ntris):
+    """test_build_host's QNode4 checks without a loop over the nodes: children
+    after parents and referred to once, leaves tile the triangles once, an
+    empty child is all 0xFFFF, every decoded box holds the padded box of the
+    BVH2 (node, side) of its range with a grid step to spare."""
+    nq = len(q4)
+    child = q4["child"].astype(np.int64)
+    none = child == rh.KNOCHILD
+    assert (q4["q"][none] == 0xFFFF).all()
+    inner, leaf = child >= 0, (child < 0) & ~none
+    assert np.array_equal(np.sort(child[inner]), np.arange(1, nq))
+    assert (child[inner] > np.nonzero(inner)[0]).all()
+    u = (~child[leaf]) & 0xFFFFFFFF
+    o = np.argsort(u >> 2, kind="stable")
+    first, cnt = (u >> 2)[o], ((u & 3) + 1)[o]
+    assert first[0] == 0 and np.array_equal(first[1:], (first + cnt)[:-1])
+    assert first[-1] + cnt[-1] == ntris
+    assert (grid[3:] > 0).all() and np.isfinite(grid).all()
+    # (range) -> BVH2 (node, side)
+    nkey = (rng[:, :, 0] << 32 | rng[:, :, 1]).reshape(-1)
+    order = np.argsort(nkey, kind="stable")
+    qr = q4_ranges_by_level(q4)
+    qkey = (qr[:, :, 0] << 32 | qr[:, :, 1])[~none]
+    at = np.searchsorted(nkey[order], qkey)
+    assert np.array_equal(nkey[order][at], qkey)
+    src = order[at]
+    slo, shi = plo.reshape(-1, 3)[src].astype(np.float64), phi.reshape(-1, 3)[src].astype(np.float64)
+    scale = grid[3:].astype(np.float64)
+    dlo = rh.decode_q(grid, q4["q"][:, :, :3][~none])
+    dhi = rh.decode_q(grid, q4["q"][:, :, 3:][~none])
+    assert (dlo + scale <= slo).all() and (dhi - scale >= shi).all()
 
 
 # ---- GPU helpers (test_gpu_refit.py's, restated: that file stays as it is) ----

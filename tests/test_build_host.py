@@ -31,7 +31,9 @@ def test_mesh_shapes(meshes, built):
     assert len(built["tri4"]["nodes"]) == 1
     assert len(built["tri5"]["nodes"]) >= 1 and (built["tri5"]["nodes"]["left"] < 0).any()
     assert len(built["grid12"]["tris"]) == 288 and len(built["grid12"]["nodes"]) > 32
-    assert len(built["wavelet0"]["nodes"]) > 512  # levels wider than one workgroup
+    # more nodes in all than one workgroup has threads; no BFS level is wider than
+    # about 100 (levels beyond 512: build_cases.py)
+    assert len(built["wavelet0"]["nodes"]) > 512
     # stairs: codes 2^k, k = 0..29, five zeros and the far corner
     v, f = meshes["stairs"]
     codes = np.sort(bh.sort_keys(v, f) >> np.uint64(32))
