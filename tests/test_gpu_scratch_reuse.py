@@ -1,6 +1,9 @@
 """The batched slot calls in one sequence on ONE context: isosurface, build and
 refit share the staging buffer and each reuse their own scratch arena
-(job_arena.h), smaller calls after larger ones and the other way round.
+(job_arena.h), smaller calls after larger ones and the other way round.  The
+arenas that came later (recolor, tet, cell, surf, clip, stream, glyph,
+bstream), the scratch the filters share between them and a live in-situ
+engine over changing slots are test_gpu_session.py's.
 
 Every step is checked by the slots' exported bytes against the host
 restatements: spray_rt_bvh_build_device_host for built slots (of the arrays
